@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- kriged grid-points/sec (z + sigma^2) of the HIP execute() path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--no-cpu] [--moving-window K]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--moving-window K] [--dump-outputs DIR] [--full [--no-cpu]]
+
+A plain run sets up, warms up, times K steps and prints the result line; --dump-outputs DIR also writes what the last timed
+step returned (DIR/z.npy, DIR/ss.npy).  --full adds everything else the line can report, each after the timed steps: live PMC
+traffic (rocprofv3), the resident-points and points-style rates, BASELINE's other configurations and the moving window (config 2,
+1 GPU), the CPU baseline and the bounded whole-grid parity check against the reference.
 
 One "step" = ONE call of the drop-in class's execute('grid', axes) end to end ("wall-clock of execute()"):
 host front matter, the grid generated on the device from its axes (mik_set_grid: what crosses PCIe on the way in is
@@ -588,6 +593,22 @@ def scalars_for_driver(out):
     return c
 
 
+def dump_outputs(d, arrays, suffix="", limit=64 << 20):
+    """--dump-outputs: the arrays a caller of the timed path received, flattened, as float64 d/<name><suffix>.npy.  When they
+    exceed `limit` bytes together, every array keeps the same fixed, seeded sample of flat indices instead (sorted; written as
+    d/sample_index<suffix>.npy, float64), so that two runs with the same arguments are compared point for point."""
+    os.makedirs(d, exist_ok=True)
+    flat = {k: np.ascontiguousarray(np.ma.getdata(a), dtype=np.float64).ravel() for k, a in arrays.items()}
+    n = min(a.size for a in flat.values())
+    if sum(a.nbytes for a in flat.values()) > limit:
+        keep = limit // (8 * (len(flat) + 1))
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        flat = {k: a[idx] for k, a in flat.items()}
+        flat["sample_index"] = idx.astype(np.float64)
+    for k, a in flat.items():
+        np.save(os.path.join(d, k + suffix + ".npy"), a)
+
+
 MW_KERNELS = {1: "k_mw_chol", 2: "k_mw_solve", 3: "k_mw_solve_big", 4: "k_mw_chol_blocked"}
 FACTOR_PATHS = {1: "spd-shift block sweep", 2: "pivoted block gauss-jordan", 3: "caller-supplied inverse", 4: "device pseudo-inverse (jacobi)",
                 5: "deflated inverse (pseudo-inverse of duplicated stations)", 6: "deflated inverse (numerically found null space)"}
@@ -599,13 +620,19 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)  # (the part's clock settles over the first second of load)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that are not the headline: live PMC passes, resident-points and "
+                         "points-style rates, other configs, CPU baseline, whole-grid parity (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write z and sigma^2 of the last timed step as DIR/z.npy and DIR/ss.npy (float64; a fixed, seeded sample "
+                         "of the points, with their flat indices in DIR/sample_index.npy, when the whole grid exceeds 64 MB)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-sample", type=int, default=4096, help="points of the bounded CPU slab")
     ap.add_argument("--cpu-protocol", choices=["bounded", "full"], default="full",
                     help="full (default) = BASELINE.md section 3 to the letter (>= 16 384-point slab, best of 3, thread sweep): about a "
                          "minute of CPU time; bounded = the same protocol on --cpu-sample points")
     ap.add_argument("--pmc", choices=["auto", "on", "off"], default="auto",
-                    help="collect roofline.traffic live with two rocprofv3 --pmc passes of one step (auto: when N = 1)")
+                    help="--full: collect roofline.traffic live with two rocprofv3 --pmc passes of one step (auto: when N = 1)")
     ap.add_argument("--exchange", choices=sorted(EXCHANGE_CODES), default=os.environ.get("MIK_BENCH_EXCHANGE", "auto"),
                     help="how the inverted matrix reaches the other GPUs (auto: RCCL broadcast, else peer copies)")
     ap.add_argument("--symmetric", type=int, default=None)
@@ -634,10 +661,10 @@ def main():
     ap.add_argument("--full-parity-budget", type=float, default=None, metavar="S",
                     help="--full-parity: wall-clock bound of the reference side per config (default: none, the whole grid)")
     ap.add_argument("--full-grid-budget", type=float, default=float(os.environ.get("MIK_BENCH_FULLGRID_BUDGET", "90")), metavar="S",
-                    help="default run: seconds the reference may spend on the headline's WHOLE-grid parity check after the timed steps "
+                    help="--full: seconds the reference may spend on the headline's WHOLE-grid parity check after the timed steps "
                          "(slabs spread over the grid; config.c2_fullgrid_* say how many points that covered; 0 = skip)")
     ap.add_argument("--no-other", action="store_true",
-                    help="default run (config 2, 1 GPU): do not time BASELINE configs 3-5 and the moving window after the headline")
+                    help="--full (config 2, 1 GPU): do not time BASELINE configs 3-5 and the moving window after the headline")
     args = ap.parse_args()
     inner = os.environ.get("MIK_BENCH_INNER") == "1"  # a rocprofv3 pass of collect_traffic_live: no CPU leg, no recursion
     if args.full_parity:
@@ -876,6 +903,9 @@ def main():
     dt = time.perf_counter() - t0
     if pg is not None:
         dt = pg.all_reduce_max(dt)
+    if args.dump_outputs:
+        progress["stage"] = "dump the last step's outputs"
+        dump_outputs(args.dump_outputs, {"z": res[0], "ss": res[1]}, suffix="_rank%d" % rank if world > 1 else "")
     if executor is not None:
         exchange = executor.exchange
     elif group > 1 and not kw:
@@ -987,7 +1017,7 @@ def main():
             out["multi_gpu"] = {"ranks": allp, "exchange_path": exchange, "rccl_ranks": world if exchange == "rccl_bcast" else 0,
                                 "exchange_bytes": last.get("exchange_bytes"), "exchange_ms": getattr(executor, "exchange_ms", None)}
         # ---- roofline.traffic: live PMC passes over one step of this benchmark, else the committed profile (labelled)
-        if n_gpus == 1 and not inner and args.pmc != "off":
+        if args.full and n_gpus == 1 and not inner and args.pmc != "off":
             progress["stage"] = "live PMC passes (rocprofv3)"
             tail = ["--steps", "1", "--warmup", "0", "--no-cpu", "--pmc", "off", "--config", str(args.config)]
             if kw:
@@ -1026,7 +1056,7 @@ def main():
         if not kw:
             # compulsory bytes of one launch: the inverse once, the RHS panel (8 M per point) in, 8 M/128 partial sums per point out
             roof["algorithmic_bytes_per_launch"] = 8.0 * (M * M + pts_per_launch * (M + M / 128.0))
-        if world == 1 and not inner:
+        if args.full and world == 1 and not inner:
             progress["stage"] = "resident-points rate and points-style rate"
             # the same work through the C ABI with the points already resident in HBM: mik_factor + mik_predict per step
             # (round 1-2 headline; what execute() costs on top of it is host_overhead above)
@@ -1062,7 +1092,7 @@ def main():
                 zg, ssg = (np.asarray(a).ravel() for a in res)
                 out["checksum"] = {"z_sum": float(zg.sum()), "ss_sum": float(ssg.sum()),
                                    "grid_vs_points_max_abs_dz": float(np.abs(zg - zz).max()), "grid_vs_points_max_abs_dss": float(np.abs(ssg - sss).max())}
-        if n_gpus == 1 and world == 1 and not inner and not kw and args.config == 2 and not args.no_other:
+        if args.full and n_gpus == 1 and world == 1 and not inner and not kw and args.config == 2 and not args.no_other:
             # BASELINE's other configurations and the moving window under the same clock (3 steps, 1 warm-up each; parity against
             # the stored reference slabs).  Keys are pinned by tests/test_bench_host.py.
             out["other_configs"] = {}
@@ -1075,7 +1105,7 @@ def main():
                     out["other_configs"][key] = other_config_line(cno, win, steps=10, warmup=3) if win else other_config_line(cno, win)
                 except Exception as e:  # noqa: BLE001
                     out["other_configs"][key] = {"value": None, "error": repr(e)[:300]}
-        if n_gpus == 1 and not args.no_cpu and not inner:
+        if args.full and n_gpus == 1 and not args.no_cpu and not inner:
             progress["stage"] = "cpu_baseline leg"
             try:
                 cb, (cp, cz, css) = cpu_baseline(cfg, coords, values, args.cpu_sample, window=kw, full=args.cpu_protocol == "full")
@@ -1094,7 +1124,7 @@ def main():
             except Exception as e:  # the bench line must still come out
                 out["cpu_baseline"] = {"value": None, "unit": "grid-points/s", "cores": None, "kind": "port",
                                        "sample": "failed: %r" % (e,)}
-        if n_gpus == 1 and world == 1 and not inner and not kw and args.config == 2 and not args.no_cpu and args.full_grid_budget > 0:
+        if args.full and n_gpus == 1 and world == 1 and not inner and not kw and args.config == 2 and not args.no_cpu and args.full_grid_budget > 0:
             # parity over the WHOLE headline grid: one execute('grid') of all 10^6 points against the reference kriging the same grid
             # slab by slab for --full-grid-budget seconds (spread over the grid; `bench.py --full-parity` = without the bound)
             progress["stage"] = "whole-grid parity against the reference"

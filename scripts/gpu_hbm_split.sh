@@ -8,8 +8,8 @@ OUT=$PWD/gpurun_out/${1:-hbm_split}; mkdir -p $OUT; REPO=$PWD
 cd /tmp && export TMPDIR=/tmp
 CTR="TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_RDREQ_DRAM_sum TCC_EA0_RDREQ_32B_sum"
 timeout 200 rocprofv3 --kernel-trace --pmc $CTR --output-format csv -d $OUT/probe -o probe -- $REPO/tools/ea_probe > $OUT/probe.txt 2> $OUT/probe.err
-timeout 300 rocprofv3 --kernel-trace --pmc $CTR --output-format csv -d $OUT/bench -o bench -- python $REPO/bench.py --steps 1 --warmup 1 --no-cpu --pmc off --no-other > $OUT/bench.json 2> $OUT/bench.err
-timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o fetch -- python $REPO/bench.py --steps 1 --warmup 1 --no-cpu --pmc off --no-other > /dev/null 2>> $OUT/bench.err
+timeout 300 rocprofv3 --kernel-trace --pmc $CTR --output-format csv -d $OUT/bench -o bench -- python $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu --pmc off --no-other > $OUT/bench.json 2> $OUT/bench.err
+timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o fetch -- python $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu --pmc off --no-other > /dev/null 2>> $OUT/bench.err
 cd $REPO
 python scripts/hbm_split.py $OUT > $OUT/hbm_split.txt 2>&1
 cat $OUT/probe.txt $OUT/hbm_split.txt

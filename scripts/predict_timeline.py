@@ -2,7 +2,7 @@
 which HSA queue (= stream), how long each waited behind the one before it on its queue, and where the prediction's wall time goes that is
 not contraction (round-5 review: predict_total 40.6 ms against 36.2 ms of k_contract_spg; memsets at 0.5 ms, k_ss_reduce_sp at 1 ms).
 
-    cd /tmp && rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python bench.py --config 5 --steps 2 --warmup 1 --no-cpu --pmc off --no-other
+    cd /tmp && rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python bench.py --full --config 5 --steps 2 --warmup 1 --no-cpu --pmc off --no-other
     python scripts/predict_timeline.py DIR [full]
 """
 import csv

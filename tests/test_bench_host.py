@@ -126,7 +126,7 @@ def test_tracked_pmc_summary_contains_the_dominant_kernel():
 
 
 def test_other_configs_key_set_and_trial_flags_are_pinned():
-    """Round 4: the default N = 1 run also times BASELINE configs 3, 4, 5 and the moving window (k = 10, 100) and checks each against
+    """Round 4: the N = 1 run with --full also times BASELINE configs 3, 4, 5 and the moving window (k = 10, 100) and checks each against
     the stored reference slab; the line's key set is what the driver's BENCH record will show."""
     src = open(os.path.join(ROOT, "bench.py")).read()
     for key in ("config3", "config4", "config5", "moving_window_k10", "moving_window_k100"):
@@ -267,3 +267,19 @@ def test_cpu_leg_times_the_reference_itself_where_it_is_staged():
         assert out["vectorized"]["port_vs_reference_max_abs_dz"] < 1e-9 and out["vectorized"]["port_vs_reference_max_abs_dss"] < 1e-9
         ax = bench.row_slab_axes(cfg, 96)
         assert pts.shape[0] == int(np.prod([a.size for a in ax])) == z.size
+
+
+def test_dumped_outputs_are_float64_and_a_fixed_sample_beyond_the_limit(tmp_path):
+    """--dump-outputs: the whole arrays while they fit the limit; beyond it the same seeded sample of flat indices from every array, run after run."""
+    z, ss = np.arange(6.0).reshape(2, 3), np.ma.masked_array(np.arange(6.0) * 2.0, mask=[0, 1, 0, 0, 0, 0])
+    bench.dump_outputs(str(tmp_path / "whole"), {"z": z, "ss": ss})
+    assert np.load(tmp_path / "whole" / "z.npy").tolist() == z.ravel().tolist()
+    assert np.load(tmp_path / "whole" / "ss.npy").dtype == np.float64 and not (tmp_path / "whole" / "sample_index.npy").exists()
+    big = {"z": np.arange(1000.0), "ss": -np.arange(1000.0)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big, suffix="_rank1", limit=8 * 3 * 100)
+    idx = np.load(tmp_path / "a" / "sample_index_rank1.npy")
+    assert idx.size == 100 and np.array_equal(idx, np.load(tmp_path / "b" / "sample_index_rank1.npy")) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "z_rank1.npy"), idx) and np.array_equal(np.load(tmp_path / "a" / "ss_rank1.npy"), -idx)
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert '"--full"' in src and '"--dump-outputs"' in src

@@ -35,7 +35,9 @@ def _run(tmp_path, files):
         z.extractall(tmp_path)
     (tmp_path / "conftest.py").write_text(SHIM % ROOT)
     xml = tmp_path / "report.xml"
-    env = dict(os.environ, PYTHONPATH=ROOT, MPLBACKEND="Agg")
+    # test_api.py grid-searches with n_jobs=-1: joblib starts one worker per CPU, and every worker kriges on the GPU.  A GPU serves
+    # at most 16 processes; LOKY_MAX_CPU_COUNT caps the count joblib sees (the search and its scores are the same with fewer workers).
+    env = dict(os.environ, PYTHONPATH=ROOT, MPLBACKEND="Agg", LOKY_MAX_CPU_COUNT="4")
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", "--junitxml", str(xml), "-o", "junit_family=xunit1"]
                        + ["tests/" + f for f in files], cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=1500)
     assert xml.exists(), (r.stdout[-3000:], r.stderr[-3000:])

@@ -40,9 +40,20 @@ def _budget(cno):
     return max(5.0, min(BUDGET_S[cno] * scale, left * BUDGET_S[cno] / later))
 
 
+@pytest.fixture
+def one_checker_at_a_time(tmp_path_factory):
+    """Under pytest-xdist the configs may land on different workers: their reference pools are sized by the host's free memory
+    as each finds it, so they take turns (an flock in the directory every worker's temporary directory lives in)."""
+    import fcntl
+
+    with open(str(tmp_path_factory.getbasetemp().parent / "whole_grid_checker.lock"), "w") as f:
+        fcntl.flock(f, fcntl.LOCK_EX)
+        yield
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("cno", ORDER)
-def test_whole_grid_against_the_reference(cno):
+def test_whole_grid_against_the_reference(cno, one_checker_at_a_time):
     if not rp.available():
         pytest.fail("oracle/_ref is not staged: run oracle/build_ref.sh (or __graft_entry__.build()) where /root/reference exists")
     budget = _budget(cno)
