@@ -342,6 +342,24 @@ int  mik_take_results(mik_handle *h, double **z, double **ss); /* the same witho
                                                               from released ones) for its next predict.  One device, no mask;
                                                               otherwise MIK_ESTATE and mik_get_results is the call */
 void mik_release_results(double *z);                       /* gives such a buffer back (any thread) */
+
+/* Several value fields on one station set (daily values of a fixed network, ensemble members, species, bootstrap replicates).
+ * z depends on the values only through c = A_inv[:, :n] Z; the matrix, its inverse, the right-hand sides and sigma^2 do not.
+ * mik_set_fields hands the handle nf fields of n values, FIELD-MAJOR (field f is values + f * n, the same station order as
+ * mik_problem.values); nf = 0 clears them and the handle behaves exactly as without.  The fields are copied (every member of a
+ * device group gets them) and stay until the next mik_set_fields or mik_set_problem (which clears them).  With fields set,
+ * mik_predict forms C = A_inv[:, :n] V (Mp x nf) on every device from that device's own copy of the inverse (k_cvec<8>: eight
+ * columns per read of A_inv; column f is bit for bit the c of a problem whose values are field f), kriges field 0 as the
+ * values of the problem (mik_get_results / mik_take_results return field 0 and sigma^2) and the other fields from the
+ * right-hand-side panel each launch has just written, eight per pass (k_rhs<0, 0, SP, false, 8>): no variogram is evaluated
+ * twice, sigma^2 is computed once.  z of field f is bit for bit the z of a mik_predict whose factor was formed with field f as
+ * the problem's values -- the variogram and the drift set-up are the problem's, and so is the factor path the probe of the
+ * inverse chose (it tests the problem's own values).  The planes of fields 1 .. nf - 1 go to a page-locked landing zone chunk by chunk,
+ * as z does.  Not with mik_predict_moving_window (MIK_EINVAL). */
+int  mik_set_fields(mik_handle *h, const double *values, int64_t n, int32_t nf);
+int  mik_get_field_results(mik_handle *h, double *z_out);  /* nf x npt doubles, plane f = field f, each scattered through the mask like
+                                                              mik_get_results (masked points 0.0 in every plane); call it before
+                                                              mik_take_results */
 int  mik_synchronize(mik_handle *h);                       /* wait until the handle's stream is idle (every call above
                                                               already blocks; this is the explicit bracket for timing) */
 

@@ -93,6 +93,8 @@ SIGNATURES = {
     "mik_get_results": (C.c_int, [C.c_void_p, _dp, _dp]),
     "mik_take_results": (C.c_int, [C.c_void_p, C.POINTER(_dp), C.POINTER(_dp)]),
     "mik_release_results": (None, [_dp]),
+    "mik_set_fields": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32]),
+    "mik_get_field_results": (C.c_int, [C.c_void_p, _dp]),
     "mik_synchronize": (C.c_int, [C.c_void_p]),
     "mik_set_custom_variogram": (C.c_int, [C.c_void_p, VARIOGRAM_FN, C.c_void_p]),
     "mik_predict_moving_window": (C.c_int, [C.c_void_p, C.c_int]),
@@ -409,6 +411,22 @@ class Handle:
         ss = np.empty(n, dtype=np.float64)
         check(self._lib.mik_get_results(self._h, _ptr(z), _ptr(ss)))
         return z, ss
+
+    def set_fields(self, values):
+        """mik_set_fields: `values` (nf, n) float64, one field per row; None clears the fields."""
+        if values is None:
+            self._fields = None
+            check(self._lib.mik_set_fields(self._h, None, 0, 0))
+            return
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        check(self._lib.mik_set_fields(self._h, _ptr(v), int(v.shape[1]), int(v.shape[0])))
+        self._fields = int(v.shape[0])
+
+    def get_field_results(self):
+        """z of every field of the last predict, (nf, npt); before get_results (mik_take_results hands the results over)."""
+        z = np.empty((self._fields, self._npt), dtype=np.float64)
+        check(self._lib.mik_get_field_results(self._h, _ptr(z)))
+        return z
 
     def timing(self):
         t = MikTiming()

@@ -323,6 +323,14 @@ struct mik_handle {
   bool points_adjusted = false;   // mik_adjust_points has transformed the resident points (a second call would transform them twice)
   DevBuf Averify, vbuf;
   std::vector<double> hvals;   // host copy of the station values (the probe compares A c with them)
+  // several value fields (mik_set_fields): nf fields of N values, field-major on the host; on the device the fields padded with zero
+  // columns to a multiple of MIK_FB, in the order of the factor's stations (fv_sorted), and C = A_inv[:, :N] V, formed by mik_predict
+  int nf = 0;
+  std::vector<double> hfields;
+  DevBuf fv, fc, zf;     // V (nfp x N), C (nfp x Mp), z of fields 1 .. nf - 1 (planes of npt; field 0 is z)
+  PinBuf pin_fz;         // page-locked landing zone of zf (mik_get_field_results reads it, plane 0 from pin_out)
+  int fv_sorted = -1;    // order of the stations in fv: 0 caller's, 1 Hilbert-curve (sort_perm), -1 not uploaded
+  int nf_done = 0;       // fields the last mik_predict kriged (0: none; mik_get_field_results needs it > 0)
   // look-ahead sweep (from 3 block columns on): the next diagonal block is built and inverted ahead of the panel / update stream
   // ("early diagonal" schedule; the schedules it replaced -- rounds 1-2 -- and its flag-ordered variants left the library in round 6)
   int opt_gate = -1;       // look-ahead sweep: the trailing update waits until the next diagonal inverse has started and leaves
@@ -482,6 +490,7 @@ int launch_mirror_upper(double* T, long Mp, hipStream_t st);                    
 int one_factor(mik_handle* h);                                                                                   // mik_inverse.hip
 int sort_points(mik_handle* h, long chunk, long nchunks);                                                        // mik_predict.hip
 int one_predict(mik_handle* h);                                                                                  // mik_predict.hip
+int fields_coefficients(mik_handle* h);                                                                          // mik_predict.hip
 int one_predict_mw(mik_handle* h, int n_closest);
 // mik_mw_chol.hip, part N: launches class 100 G + RI of k_mw_chol if it holds it, else returns MIK_MWC_NOCLASS
 #define MIK_MWC_PARTS 5

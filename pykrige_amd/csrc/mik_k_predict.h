@@ -44,10 +44,22 @@ struct RhsArgs {
                          // 12 % slower: half-line stores)
   const unsigned* perm;  // SP, nullable: the chunk's points in sorted order -- point t of the chunk is point perm[t] of the WHOLE list;
                          // px / py / pz / extra / zout are then the list's base pointers, not the chunk's (option "sort_points")
+  long cf_ld;  // read-back of several fields (FC > 0, mik_k_fields.h): column stride of the coefficients at cvec
+  long zf_ld;  //   ... plane stride of the outputs at zout
+  int nfc;     //   ... fields of this launch that exist (<= FC)
 };
+}  // namespace mik
+#include "mik_k_fields.h"
+namespace mik {
 
-template <int MODEL, int NDIM, bool SP = false, bool F8 = false>  // F8 (SP only): flags per 8 stations (row stride nKf) instead of per 16
+// F8 (SP only): flags per 8 stations (row stride nKf) instead of per 16.  FC > 0: no right-hand sides -- the z of FC more fields from
+// the panel this launch's k_rhs wrote (rhs_fields, mik_k_fields.h; MODEL and NDIM are then 0)
+template <int MODEL, int NDIM, bool SP = false, bool F8 = false, int FC = 0>
 __global__ void __launch_bounds__(256) k_rhs(RhsArgs a) {
+  if constexpr (FC > 0) {
+    rhs_fields<SP, FC>(a);
+    return;
+  }
   __shared__ double red[4][MIK_TP];
   const int t0 = blockIdx.x * MIK_TP;
   double qx[MIK_TP], qy[MIK_TP], qz[MIK_TP];

@@ -45,6 +45,37 @@ int sort_points(mik_handle* h, long chunk, long nchunks) {
   return MIK_OK;
 }
 
+// Several value fields (mik_set_fields): C = A_inv[:, :N] V from this device's own copy of the inverse, MIK_FB columns per block of
+// k_cvec<MIK_FB> (column f is bit for bit the k_cvec of field f).  V goes up once per set of fields and station order.
+int fields_coefficients(mik_handle* h) {
+  // columns: a multiple of MIK_FB that also holds the last read-back launch's (fields 1 + MIK_FB k .. MIK_FB (k + 1), see one_predict)
+  const int nf = h->nf, nfp = ((nf - 1 + MIK_FB - 1) / MIK_FB) * MIK_FB + MIK_FB;
+  const long N = h->N;
+  const int want = h->factor_sorted ? 1 : 0;
+  if (h->fv_sorted != want) {
+    if (want && (long)h->sort_perm.size() != N) return fail(MIK_ESTATE, "mik_predict: station order of the factor unknown");
+    std::vector<double> v((size_t)nfp * (size_t)N, 0.0);
+    for (int f = 0; f < nf; ++f) {
+      const double* src = h->hfields.data() + (size_t)f * N;
+      double* dst = v.data() + (size_t)f * N;
+      if (want) {
+        for (long i = 0; i < N; ++i) dst[i] = src[h->sort_perm[(size_t)i]];
+      } else {
+        memcpy(dst, src, sizeof(double) * (size_t)N);
+      }
+    }
+    MIKC(h->fv.ensure(sizeof(double) * v.size()));
+    HIPC(hipMemcpyAsync(h->fv.p, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, h->stream));
+    HIPC(hipStreamSynchronize(h->stream));  // v is a local
+    h->fv_sorted = want;
+  }
+  MIKC(h->fc.ensure(sizeof(double) * (size_t)nfp * (size_t)h->Mp));
+  hipLaunchKernelGGL((k_cvec<MIK_FB>), dim3((h->Mp + 3) / 4, nfp / MIK_FB), dim3(256), 0, h->stream, (const double*)h->T.as<double>(),
+                     (long)h->Mp, h->M, h->N, (const double*)h->fv.as<double>(), (long)N, h->fc.as<double>(), (long)h->Mp, h->Mp);
+  HIPC(hipGetLastError());
+  return MIK_OK;
+}
+
 int one_predict(mik_handle* h) {
   if (!h || !h->have_factor) return fail(MIK_ESTATE, "mik_predict: factor first");
   if (!h->have_points) return fail(MIK_ESTATE, "mik_predict: set points first");
@@ -57,9 +88,17 @@ int one_predict(mik_handle* h) {
   h->tm.symmetric = h->opt_sym;
   h->tm.engine = 0;  // (the v_fma_f64 contraction left the library in round 6: tools/kernel_bench)
   h->tm.mw_kernel = 0;
+  const int nf = h->nf;  // value fields (mik_set_fields): field 0 goes to z, the others to the planes of zf
+  h->nf_done = nf;
   if (npt == 0) {
     h->have_results = true;
     return MIK_OK;
+  }
+  if (nf > 1) {
+    MIKC(h->zf.ensure(sizeof(double) * (size_t)(nf - 1) * (size_t)npt));
+    // page-locked landing zone of fields 1 .. nf - 1, filled chunk by chunk like pin_out (an earlier predict's copies may still write it)
+    HIPC(hipEventSynchronize(h->ev_d2h));
+    MIKC(h->pin_fz.ensure(sizeof(double) * (size_t)(nf - 1) * (size_t)npt));
   }
   long chunk = std::min<long>(h->opt_chunk, ((npt + 127) / 128) * 128);
   if (h->model == MIK_MODEL_CUSTOM) chunk = std::min<long>(chunk, 16384);  // each chunk's distances visit the host
@@ -151,6 +190,9 @@ int one_predict(mik_handle* h) {
   hipStream_t sr = two ? h->stream2 : h->stream;  // right-hand sides
   HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));  // an earlier predict's result copies still read z / ss
   if (sparse && h->geo) MIKC(geo_point_vectors(h));  // what the candidate boxes of a geographic problem are built from
+  // C of the fields first: the second stream (two right-hand-side panels, the second lane of the range-aware path) starts at evpool[0], and
+  // every k_rhs reads C
+  if (nf > 0) MIKC(fields_coefficients(h));
   HIPC(hipEventRecord(h->evpool[0], h->stream));
   bool sorted_now = false;
   if (sortpts && !(h->ps_valid && h->ps_chunk == chunk)) {
@@ -191,8 +233,23 @@ int one_predict(mik_handle* h) {
     a.wells = h->wells.as<double>();
     a.extra = h->nextra ? h->extra_rows.as<double>() + t0 : nullptr;
     a.extra_stride = npt;
-    a.cvec = h->cvec.as<double>();
+    a.cvec = nf > 0 ? (const double*)h->fc.as<double>() : (const double*)h->cvec.as<double>();
     a.zout = h->z.as<double>() + t0;
+    // fields 1 .. nf - 1: MIK_FB per launch, read back from the panel the launch of field 0 has just written (same stream, right after it)
+    auto launch_fields = [&](const RhsArgs& a0, bool sp, hipStream_t st) -> int {
+      for (int f0 = 1; f0 < nf; f0 += MIK_FB) {
+        RhsArgs b = a0;
+        b.cvec = h->fc.as<double>() + (size_t)f0 * Mp;
+        b.cf_ld = Mp;
+        b.nfc = std::min(MIK_FB, nf - f0);
+        b.zout = h->zf.as<double>() + (size_t)(f0 - 1) * npt + (sp && b.perm ? 0 : t0);
+        b.zf_ld = npt;
+        if (sp) hipLaunchKernelGGL((k_rhs<0, 0, true, false, MIK_FB>), dim3(palloc / MIK_TP), dim3(256), 0, st, b);
+        else hipLaunchKernelGGL((k_rhs<0, 0, false, false, MIK_FB>), dim3(palloc / MIK_TP), dim3(256), 0, st, b);
+      }
+      HIPC(hipGetLastError());
+      return MIK_OK;
+    };
     if (two && c >= 2) HIPC(hipStreamWaitEvent(sr, h->pr_events[2 * (c - 2) + 1], 0));  // the contraction that read this panel is done
     if (sparse) {
       // candidates (bounding boxes), cleared flags, then delta for the candidate blocks only
@@ -233,6 +290,7 @@ int one_predict(mik_handle* h) {
       } else if (h->geo) hipLaunchKernelGGL((k_rhs<3, 1, true>), dim3(palloc / MIK_TP), dim3(256), 0, ss, a);
       else if (h->ndim == 3) hipLaunchKernelGGL((k_rhs<3, 3, true>), dim3(palloc / MIK_TP), dim3(256), 0, ss, a);
       else hipLaunchKernelGGL((k_rhs<3, 2, true>), dim3(palloc / MIK_TP), dim3(256), 0, ss, a);
+      MIKC(launch_fields(a, true, ss));
       HIPC(hipEventRecord(h->evpool[3 + 4 * c], ss));
       return MIK_OK;
     }
@@ -244,8 +302,16 @@ int one_predict(mik_handle* h) {
     } else {
       DISPATCH_MODEL_NDIM(h->model, h->geo ? 1 : h->ndim, k_rhs, dim3(palloc / MIK_TP), dim3(256), sr, a);
     }
+    MIKC(launch_fields(a, false, sr));
     HIPC(hipEventRecord(h->evpool[3 + 4 * c], sr));
     if (two) HIPC(hipEventRecord(h->pr_events[2 * c], sr));
+    return MIK_OK;
+  };
+  // a chunk's z of fields 1 .. nf - 1 leave for pin_fz beside its z and sigma^2 (on stream_d2h, behind ev_chunk)
+  auto copy_fields_out = [&](long t0, int nvalid) -> int {
+    for (int f = 1; f < nf; ++f)
+      HIPC(hipMemcpyAsync(h->pin_fz.as<double>() + (size_t)(f - 1) * npt + t0, h->zf.as<double>() + (size_t)(f - 1) * npt + t0,
+                          sizeof(double) * nvalid, hipMemcpyDeviceToHost, h->stream_d2h));
     return MIK_OK;
   };
   if (two) MIKC(launch_rhs(0));
@@ -364,6 +430,7 @@ int one_predict(mik_handle* h) {
                           h->stream_d2h));
       HIPC(hipMemcpyAsync(h->pin_out.as<double>() + npt + t0, h->ss.as<double>() + t0, sizeof(double) * nvalid,
                           hipMemcpyDeviceToHost, h->stream_d2h));
+      MIKC(copy_fields_out(t0, nvalid));
       h->tm.sparse_tiles_dense += (double)nTb * nIblk;
       h->tm.sparse_ktiles_dense += (double)nTb * (kend / 16.0) * (nIblk - 1) / 2.0;  // off-diagonal K tiles of the dense symmetric form (about)
       continue;
@@ -400,6 +467,7 @@ int one_predict(mik_handle* h) {
                         h->stream_d2h));
     HIPC(hipMemcpyAsync(h->pin_out.as<double>() + npt + t0, h->ss.as<double>() + t0, sizeof(double) * nvalid,
                         hipMemcpyDeviceToHost, h->stream_d2h));
+    MIKC(copy_fields_out(t0, nvalid));
     // executed flops of this launch: per tile 2*128*128*(k extent)
     // (triangular diagonal blocks: nt (nt + 1) / 2 products of 16 rows x 16 k instead of 8 nt, nt = K tiles of the block)
     const bool tri = h->opt_sym && h->opt_tri;

@@ -115,10 +115,11 @@ static void destroy_one(mik_handle* h) {
                     &h->px, &h->py, &h->pz, &h->grid_axes, &h->grid_idx, &h->Averify, &h->vbuf, &h->extra_rows, &h->z, &h->ss, &h->Bt, &h->Bt2, &h->part, &h->mw_idx, &h->mw_dist, &h->stat_S, &h->stat_x, &h->stat_out, &h->queue,
                     &h->xs_s, &h->ys_s, &h->zs_s, &h->vals_s, &h->extra_cols_s, &h->sbox, &h->sp_cand, &h->sp_flags, &h->sp_klist, &h->sp_kcount,
                     &h->sp_nrows, &h->sp_rows, &h->sp_rstart, &h->sp_tiles, &h->sp_xoff, &h->sp_stats, &h->sp2_cand, &h->sp2_flags, &h->sp2_klist, &h->sp2_kcount,
-                    &h->sp2_nrows, &h->sp2_rows, &h->sp2_rstart, &h->sp2_tiles, &h->sp2_xoff, &h->part2, &h->queue2, &h->dsc, &h->sp_recs, &h->sp2_recs, &h->ps_key[0], &h->ps_key[1], &h->ps_idx[0], &h->ps_idx[1], &h->ps_table, &h->ps_box, &h->ps_x, &h->ps_y, &h->ps_z, &h->ps_zs, &h->ps_sss, &h->xpack};
+                    &h->sp2_nrows, &h->sp2_rows, &h->sp2_rstart, &h->sp2_tiles, &h->sp2_xoff, &h->part2, &h->queue2, &h->dsc, &h->sp_recs, &h->sp2_recs, &h->ps_key[0], &h->ps_key[1], &h->ps_idx[0], &h->ps_idx[1], &h->ps_table, &h->ps_box, &h->ps_x, &h->ps_y, &h->ps_z, &h->ps_zs, &h->ps_sss, &h->xpack, &h->fv, &h->fc, &h->zf};
   for (DevBuf* b : bufs) b->release();
   h->pin_in.release();
   h->pin_out.release();
+  h->pin_fz.release();
   for (hipEvent_t e : h->evpool) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->la_events) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ps_events) (void)hipEventDestroy(e);
@@ -580,6 +581,9 @@ static int one_set_problem(mik_handle* h, const mik_problem* p) {
     HIPC(hipMemcpyAsync(h->dsc.p, h->hdsc.data(), sizeof(double) * h->hdsc.size(), hipMemcpyHostToDevice, h->stream));
   }
   HIPC(hipStreamSynchronize(h->stream));
+  h->nf = 0;  // value fields belong to a station set (mik_set_fields)
+  h->hfields.clear();
+  h->fv_sorted = -1;
   h->have_problem = true;
   h->have_factor = false;
   h->t_state = 0;
@@ -1575,6 +1579,8 @@ int mik_predict(mik_handle* h) {
 
 int mik_predict_moving_window(mik_handle* h, int n_closest) {
   if (!h) return fail(MIK_ESTATE, "mik_predict_moving_window: NULL handle");
+  if (h->nf > 0) return fail(MIK_EINVAL, "mik_predict_moving_window: value fields are set (mik_set_fields); the moving window kriges one field");
+  for (int i = 0; i <= (int)h->kids.size(); ++i) member(h, i)->nf_done = 0;
   MIKC(join_exchange(h));
   return for_each_device(h, [n_closest](int, mik_handle* d) { return one_predict_mw(d, n_closest); });
 }
@@ -1755,6 +1761,80 @@ int mik_get_results(mik_handle* h, double* z_out, double* ss_out) {
     });
   }
   return for_each_device(h, [=](int, mik_handle* d) { return one_get_results(d, z_out, ss_out); });
+}
+
+int mik_set_fields(mik_handle* h, const double* values, int64_t n, int32_t nf) {
+  if (!h) return fail(MIK_EINVAL, "mik_set_fields: NULL handle");
+  if (nf < 0 || (nf > 0 && !values)) return fail(MIK_EINVAL, "mik_set_fields: nf < 0 or values NULL");
+  if (nf > 0 && !h->have_problem) return fail(MIK_ESTATE, "mik_set_fields: set the problem first");
+  if (nf > 0 && n != h->N) return fail(MIK_EINVAL, "mik_set_fields: n = " + std::to_string((long long)n) + " differs from the problem's " + std::to_string(h->N) + " stations");
+  if (nf > 0 && (double)nf * (double)n > 2e9) return fail(MIK_EINVAL, "mik_set_fields: nf x n too large");
+  MIKC(join_exchange(h));
+  for (int i = 0; i <= (int)h->kids.size(); ++i) {
+    mik_handle* d = member(h, i);
+    d->nf = nf;
+    if (nf > 0) d->hfields.assign(values, values + (size_t)nf * (size_t)n);
+    else d->hfields.clear();
+    d->fv_sorted = -1;
+  }
+  return MIK_OK;
+}
+
+// z of every field of one device's slab, from its page-locked landing zones (filled chunk by chunk while mik_predict ran: plane 0 in
+// pin_out, the others in pin_fz) straight into the caller's planes (stride ntot) at the slab's place.  Several fields: one host thread
+// per group of planes (the caller's pages are first touched here); one field: the plane is cut like mik_get_results cuts it
+static int one_get_field_results(mik_handle* h, double* out, long ntot) {
+  HIPC(hipSetDevice(h->device));
+  HIPC(hipEventSynchronize(h->ev_d2h));
+  const long n = h->npt;
+  const int nf = h->nf_done;
+  if (n == 0) return MIK_OK;
+  const double* hz = h->pin_out.as<double>();
+  const double* hf = h->pin_fz.as<double>();
+  auto plane = [&](int f, bool inner_threads) {
+    const double* src = f == 0 ? hz : hf + (size_t)(f - 1) * n;
+    double* dst = out + (size_t)f * ntot;
+    if (h->scatter32 || !h->scatter.empty()) {
+      auto body = [&](int, long b, long e) {
+        if (h->scatter32) {
+          for (long i = b; i < e; ++i) dst[h->scatter32[i]] = src[i];
+        } else {
+          for (long i = b; i < e; ++i) dst[h->scatter[(size_t)i]] = src[i];
+        }
+      };
+      if (inner_threads) parallel_chunks(n, body);
+      else body(0, 0L, n);
+    } else if (inner_threads) {
+      host_copy(dst + h->out_off, src, sizeof(double) * n);
+    } else {
+      memcpy(dst + h->out_off, src, sizeof(double) * n);
+    }
+  };
+  const int nthr = std::min(8, nf);
+  if (nthr < 4) {
+    for (int f = 0; f < nf; ++f) plane(f, true);
+    return MIK_OK;
+  }
+  std::vector<std::thread> th;
+  for (int t = 1; t < nthr; ++t)
+    th.emplace_back([&, t] {
+      for (int f = t; f < nf; f += nthr) plane(f, false);
+    });
+  for (int f = 0; f < nf; f += nthr) plane(f, false);
+  for (auto& t : th) t.join();
+  return MIK_OK;
+}
+
+int mik_get_field_results(mik_handle* h, double* z_out) {
+  if (!h || !z_out) return fail(MIK_EINVAL, "mik_get_field_results: NULL argument");
+  if (h->nf_done <= 0) return fail(MIK_ESTATE, "mik_get_field_results: the last predict kriged no fields (mik_set_fields)");
+  if (!h->have_results) return fail(MIK_ESTATE, "mik_get_field_results: predict first (and before mik_take_results)");
+  const long ntot = h->npt_total;
+  const size_t all = (size_t)h->nf_done * (size_t)ntot;
+  if (h->masked) {  // masked points keep 0.0 in every plane
+    parallel_chunks((long)all, [&](int, long b, long e) { memset(z_out + b, 0, sizeof(double) * (size_t)(e - b)); });
+  }
+  return for_each_device(h, [=](int, mik_handle* d) { return one_get_field_results(d, z_out, ntot); });
 }
 
 int mik_take_results(mik_handle* h, double** z_out, double** ss_out) {

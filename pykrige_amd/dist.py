@@ -426,6 +426,41 @@ class ShardedExecutor:
         return m._finish(zf, sf, style, shape, fmask, backend)
 
 
+    def execute_fields(self, style, *axes, values, mask=None, backend="vectorized", **kw):
+        """execute_fields of the model (kriging.py) with the points sharded over the ranks: every rank factors or receives the inverse as
+        execute() does, forms C = A_inv[:, :N] V from its own copy (mik_set_fields: the fields go to every rank, the factor exchange is
+        unchanged) and kriges every field on its slab.  Returns (zvalues, sigmasq) as the model's execute_fields; gather="local":
+        (zvalues of the slab (F, hi - lo), sigma^2 of the slab, (lo, hi)).  No moving window."""
+        m, h = self.model, self._handle
+        if style not in ("grid", "masked", "points"):
+            raise ValueError("style argument must be 'grid', 'points', or 'masked'")
+        m._check_backend(backend, None)
+        v = m._field_values(values)
+        P = m._prepare(style, axes, mask, kw.get("specified_drift_arrays"), backend)
+        npt, shape, fmask = P.npt, P.shape, P.mask
+        lo, hi = slab_bounds(npt, self.world, self.rank)
+        m._set_problem(h)
+        if self.exchange == "rccl_bcast":
+            self._factor_everywhere(h)
+        else:
+            h.factor()
+        P.load(h, m._ndim, cell_range=(lo, hi - lo))
+        h.set_fields(v.T)
+        try:
+            h.predict()
+            z, ss = h.get_field_results(), h.get_results()[1]
+        finally:
+            h.set_fields(None)
+        if self.gather == "local":
+            return z, ss, (lo, hi)
+        if self.world > 1:  # the slabs of every plane travel through the group (raw buffers, no pickle)
+            if hasattr(self.pg, "max_frame"):
+                self.pg.max_frame = max(self.pg.max_frame, 8 * (v.shape[1] + 1) * npt + (1 << 20))
+            parts = self.pg.all_gather_object((z, ss))
+            z, ss = np.concatenate([p[0] for p in parts], axis=1), np.concatenate([p[1] for p in parts])
+        return m._finish_fields(z, ss, style, shape, fmask, backend)
+
+
 def init_rccl(handle, pg, timeout=None):
     """Create the library's RCCL communicator on every rank of `pg`.  Returns "rccl_bcast" when every rank joined, else a
     "redundant_factor (...)" string (then every rank factors the matrix itself).  ncclCommInitRank blocks until all ranks

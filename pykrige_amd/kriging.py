@@ -260,6 +260,7 @@ class _KrigingBase:
         return self._handle
 
     _max_points = 0  # most points one call of this object handed to its handle
+    _max_fields = 0  # most fields one execute_fields call of this object handed to its handle
 
     def _handle_bytes(self):
         """Device memory the handle holds at most after this object's calls, for the parking rule: matrix, its probe copy and panels (3 Mp^2) + the
@@ -267,7 +268,9 @@ class _KrigingBase:
         n = int(np.size(self._values())) + 16
         mp = -(-n // 128) * 128
         npt = min(int(self._max_points), 131072)
-        return 8.0 * (3.0 * mp * mp + 2.0 * npt * mp + 8.0 * self._max_points + 8.0 * n)
+        nf = self._max_fields + 16  # execute_fields: the fields, their coefficients and their z planes
+        return 8.0 * (3.0 * mp * mp + 2.0 * npt * mp + 8.0 * self._max_points + 8.0 * n
+                      + (nf * (mp + n + self._max_points) if self._max_fields else 0.0))
 
     def __getstate__(self):
         """Pickling / copy.deepcopy (sklearn's clone, joblib workers, cached models): upstream's objects are plain Python attributes and travel; here the
@@ -641,6 +644,68 @@ class _KrigingBase:
             ss = np.ma.array(ss, mask=np.zeros(ss.shape, dtype=bool))
         return z.reshape(shape), ss.reshape(shape)
 
+    # ---------------------------------------------------------------- several value fields on one station set (mik_set_fields)
+    _FIELDS_DOC = """Krige F value fields measured at this object's stations in one call.
+
+        ``values`` is array-like of shape (N, F), one column per field (a 1-D (N,) array is F = 1), cast to float64.  Returns
+        ``(zvalues, sigmasq)``: ``zvalues`` has shape ``(F,) + shape`` and ``sigmasq`` ``shape``, where ``shape`` is what
+        ``execute()`` returns for the same call; the return types follow ``execute()`` (MaskedArrays for backend 'vectorized' and
+        for style 'masked', the mask repeated over the field axis; masked points are 0.0 in every plane).
+
+        The variogram is the object's: it was fitted to (or given with) the object's own values at construction and does not
+        change.  ``zvalues[f]`` is what ``execute()`` gives on an object built from the same stations and ``values[:, f]`` with
+        ``variogram_parameters`` set explicitly to this object's parameters and every other constructor argument the same
+        (drifts, anisotropy, exact_values, pseudo_inv, coordinates_type, custom callables) -- not what F objects that each fit
+        their own variogram would give.  sigma^2 does not depend on the values and is computed once.  The matrix, its inverse,
+        the right-hand sides and sigma^2 are shared by the fields, so F fields cost little more than one ``execute()``.
+        There is no moving window (n_closest_points) here."""
+
+    def _field_values(self, values):
+        n = int(np.size(self._values()))
+        v = np.array(values, copy=True, dtype=np.float64)
+        if v.ndim == 1:
+            v = v[:, None]
+        if v.ndim != 2:
+            raise ValueError("values must have shape (N,) or (N, F); got %d dimensions" % v.ndim)
+        if v.shape[0] != n:
+            raise ValueError("values has %d rows; the object has %d stations" % (v.shape[0], n))
+        if v.shape[1] == 0:
+            raise ValueError("values holds no field (F = 0)")
+        if not np.all(np.isfinite(v)):
+            raise ValueError("values holds non-finite entries")
+        return v
+
+    def _execute_fields(self, style, axes, values, mask, backend, prepare_kw):
+        """execute_fields of the four classes: every argument is checked on the host before the device is touched."""
+        if style != "grid" and style != "masked" and style != "points":
+            raise ValueError("style argument must be 'grid', 'points', or 'masked'")
+        self._check_backend(backend, None)
+        v = self._field_values(values)
+        P = self._prepare(style, axes, mask, **prepare_kw)
+        h = self._upload_and_factor()
+        self._max_points = max(self._max_points, int(np.prod(P.shape)))
+        self._max_fields = max(self._max_fields, v.shape[1])
+        P.load(h, self._ndim)
+        h.set_fields(v.T)
+        try:
+            h.predict()
+            self.last_timing = h.timing()
+            zf = h.get_field_results()  # (before get_results: that one may take the landing zone over)
+            _, ss = h.get_results()
+        finally:
+            h.set_fields(None)
+        return self._finish_fields(zf, ss, style, P.shape, P.mask, backend)
+
+    def _finish_fields(self, zf, ss, style, shape, mask, backend):
+        """_finish for the (F, npt) planes of execute_fields: the mask is repeated over the field axis."""
+        _, ss = self._finish(zf[0], ss, style, shape, mask, backend)
+        nf = zf.shape[0]
+        if style == "masked":
+            zf = np.ma.array(zf, mask=np.broadcast_to(mask, zf.shape).copy())
+        elif backend == "vectorized" and zf.size:
+            zf = np.ma.array(zf, mask=np.zeros(zf.shape, dtype=bool))
+        return zf.reshape((nf,) + tuple(shape)), ss
+
     def _spec_rows(self, style, shape, npt, specified_drift_arrays):
         """uk.py:1217-1274 / uk3d.py:1030-1095: validate + flatten the per-point specified-drift arrays."""
         if specified_drift_arrays is None:
@@ -752,6 +817,11 @@ class OrdinaryKriging(_KrigingBase):
         else:
             z, ss = self._solve(P)
         return self._finish(z, ss, style, P.shape, P.mask, backend)
+
+    def execute_fields(self, style, xpoints, ypoints, values, mask=None, backend="vectorized"):
+        return self._execute_fields(style, (xpoints, ypoints), values, mask, backend, {})
+
+    execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
 
 
 # =====================================================================================================
@@ -876,6 +946,12 @@ class UniversalKriging(OrdinaryKriging):
         z, ss = self._solve(P)
         return self._finish(z, ss, style, P.shape, P.mask, backend)
 
+    def execute_fields(self, style, xpoints, ypoints, values, mask=None, backend="vectorized", specified_drift_arrays=None):
+        return self._execute_fields(style, (xpoints, ypoints), values, mask, backend,
+                                    dict(specified_drift_arrays=specified_drift_arrays, backend=backend))
+
+    execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
+
     def _grid_rows(self, style, axes, shape, mask, specified_drift_arrays, backend):
         rows = []
         if self.external_Z_drift:  # looked up at the ORIGINAL coordinates (uk.py:967-971): the host meshgrid, for this term only
@@ -986,6 +1062,11 @@ class OrdinaryKriging3D(_KrigingBase):
             z, ss = self._solve(P)
         return self._finish(z, ss, style, P.shape, P.mask, backend)
 
+    def execute_fields(self, style, xpoints, ypoints, zpoints, values, mask=None, backend="vectorized"):
+        return self._execute_fields(style, (xpoints, ypoints, zpoints), values, mask, backend, {})
+
+    execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
+
 
 # =====================================================================================================
 class UniversalKriging3D(OrdinaryKriging3D):
@@ -1061,6 +1142,12 @@ class UniversalKriging3D(OrdinaryKriging3D):
         P = self._prepare(style, (xpoints, ypoints, zpoints), mask, specified_drift_arrays)
         z, ss = self._solve(P)
         return self._finish(z, ss, style, P.shape, P.mask, backend)
+
+    def execute_fields(self, style, xpoints, ypoints, zpoints, values, mask=None, backend="vectorized", specified_drift_arrays=None):
+        return self._execute_fields(style, (xpoints, ypoints, zpoints), values, mask, backend,
+                                    dict(specified_drift_arrays=specified_drift_arrays))
+
+    execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
 
     def _grid_rows(self, style, axes, shape, mask, specified_drift_arrays, backend):
         rows = self._spec_rows(style, shape, int(np.prod(shape)), specified_drift_arrays)
