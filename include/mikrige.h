@@ -143,7 +143,7 @@ typedef struct mik_timing {
   int32_t factor_attempts;     /* factorisations mik_factor ran: 1, or more when a bad pivot / a failed probe sent it to a more
                                   careful path (half sweep -> full sweep -> partial pivoting) */
   int32_t null_dim;            /* factor_path 6: dimension of the null space that was found and deflated */
-  int32_t rhs_overlapped;      /* 1 = two right-hand-side panels: k_rhs of chunk c + 1 ran on a second stream under chunk c's contraction */
+  int32_t rhs_overlapped;      /* always 0 (the two right-hand-side panels of option "rhs_overlap" left the library; the field keeps its place) */
   double verify_ms;            /* the probe of the inverse (all attempts) */
   double verify_res_z;         /* max |A c - [Z; 0]| / max(1, max|Z|), c = A_inv[:, :n] Z: bounds the error of z (last attempt) */
   double verify_res_inv;       /* max_j max |A_inv A e_j - e_j| over three station columns (last attempt) */
@@ -194,7 +194,8 @@ int  mik_slab_of(int64_t n, int members, int i, int64_t *lo, int64_t *count); /*
  * path; the experiments of rounds 2-5 -- "engine", "waves", "update_waves", "update_deep", "update_tpb", "update_pf", "update_token",
  * "update_map", "pivot256", "wide_reserve", "wide_colstream", "panel_rows", "diag", "early_diag", "fuse_chain", "sparse_ktile",
  * "sparse_epilogue", and before them "pairs", "prefetch", "update_atomic" -- are refused as unknown; their kernels live in
- * tools/mik_k_experiments.h or git history, their measurements in profiles/ and DESIGN_HISTORY.md):
+ * tools/mik_k_experiments.h or git history, their measurements in profiles/ and DESIGN_HISTORY.md; so are "rhs_overlap", a measured
+ * tie, and "sparse_group", fixed at 16):
  * "factor" 0=auto 1=sweep 2=pivoted ; "symmetric" 0/1 (1 = the contraction forms b^T A_inv b over one triangle of A_inv; 0 = the reference's
  *   full product w = A_inv b, ok.py:679: the cross-check kernel of the parity tests) ;
  * "exchange_tri" 0/1 = device groups / ranks: the factor exchange moves the packed UPPER BLOCK TRIANGLE of the inverse (block row I keeps its
@@ -228,8 +229,6 @@ int  mik_slab_of(int64_t n, int members, int i, int64_t *lo, int64_t *count); /*
  *   8-station tiles staged into the two halves of the 16-wide LDS tile, a 16-row group is two gathered 8-row groups, an odd last entry is
  *   half a K step (718 instead of 780 stations in active tiles at BASELINE config 5; work ~ n^2); a row group's term sum_i delta_ti W_it
  *   is formed at the K step of the group's own square from that step's B tile in LDS.  Aligned blocks keep 16-station lists ;
- * "sparse_group" 1..16 = k_contract_spg's queue order: point blocks per group (a group's tiles run on one XCD, tile position ascending
- *   = longest K loops first, point block fast; default 16) [MIK_SPARSE_GROUP] ;
  * "sort_points" -1/0/1 = range-aware contraction: the points of every launch (one chunk of the resident point list) are put in
  *   Hilbert-curve order among themselves on the device (k_ps_*: 20-bit keys, stable two-pass radix sort, all launches' segments
  *   side by side) and kriged in that order -- a block of 128 consecutive points is then a compact patch whatever order the caller's
@@ -255,8 +254,6 @@ int  mik_slab_of(int64_t n, int members, int i, int64_t *lo, int64_t *count); /*
  *   in both triangles the half product equals b^T A_inv b of the matrix as eliminated (the half sweep mirrors its triangle
  *   anyway; an inverse the caller supplies, mik_problem.a_inv, is never touched) ;
  * "chunk" = largest number of points per contraction launch (multiple of 128; the points are cut into equal launches) ;
- * "rhs_overlap" 0/1 = two right-hand-side panels: K3a of the next chunk runs on a second stream while the current chunk is
- *   contracted (default 0: measured a tie -- the contraction slows down by what K3a takes) [MIK_RHS_OVERLAP] ;
  * "lookahead" 0/1/-1 = overlap the next panel's serial chain with the current trailing update in the block sweep
  *   (default -1: from 3 block columns on).  The look-ahead schedule is the "early diagonal" one: the next diagonal block is built from 128
  *   panel rows (two distributed 128^3 products) and inverted on the second stream AHEAD of the panel kernel and update of its step; the

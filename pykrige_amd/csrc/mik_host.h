@@ -9,6 +9,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -233,6 +234,20 @@ inline int rccl_load() {
     }                                                                                              \
   } while (0)
 
+// one lane of the contraction (mik_predict.hip): right-hand-side panel Bt, partial sums, tile queues, and the range-aware path's
+// candidates, flags, lists and tiles.  The dense path uses lane 0; with "sparse_lanes" 2 the launches of the range-aware contraction
+// alternate between lane 0 (stream) and lane 1 (stream2), so that the candidate / right-hand-side / list kernels of one launch and the
+// tail of the previous launch's tile queue overlap
+struct PredictLane {
+  DevBuf cand, flags, klist, kcount, nrows, rows, rstart, tiles, xoff, recs, part, queue, Bt;
+};
+
+// the timed events of one predict launch: candidate test (range-aware path), right-hand sides, lists (range-aware path), contraction
+struct LaunchEvents {
+  hipEvent_t cand_begin = nullptr, rhs_begin = nullptr, rhs_end = nullptr, lists_end = nullptr, contract_begin = nullptr, contract_end = nullptr;
+  std::array<hipEvent_t*, 6> all() { return {&cand_begin, &rhs_begin, &rhs_end, &lists_end, &contract_begin, &contract_end}; }
+};
+
 struct mik_handle {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -264,19 +279,15 @@ struct mik_handle {
   std::vector<double> hvals_s;
   DevBuf xs_s, ys_s, zs_s, vals_s, extra_cols_s, sbox;
   int opt_sparse = -1;  // "sparse": -1 = auto (= 1: on for compact-support models), 0 = off, 1 = on, 2 = sorted stations, dense contraction
-  DevBuf sp_cand, sp_flags, sp_klist, sp_kcount, sp_nrows, sp_rows, sp_rstart, sp_tiles, sp_xoff, sp_stats, sp_recs;
+  DevBuf sp_stats;  // range-aware contraction: 4 counters per launch from k_sp_tiles / k_sp_tiles_g (tiles, K tiles, triangle products)
   int opt_sort_points = -1;  // "sort_points": range-aware contraction over the points of every launch in Hilbert-curve order (k_ps_*): -1 = auto = 1, 0 = off
   DevBuf ps_key[2], ps_idx[2], ps_table, ps_box, ps_x, ps_y, ps_z, ps_zs, ps_sss;
   DevBuf gu;  // geographic problems, range-aware contraction: unit vectors of the resident points (3 x npt)
   bool ps_valid = false;     // ps_idx[0] holds the order of the resident points for launches of ps_chunk points
   long ps_chunk = 0;
-  int opt_sparse_group = 16; // "sparse_group": point blocks per group of k_sp_tiles_g's queue order (a group's tiles run on one XCD, tile position
-                             // ascending, point block fast): 1 .. 16 (round 5: 4 -> 16, contraction 35.7 -> 35.3 ms at config 5)
   int opt_sparse_rows = -1;  // "sparse_rows": 16 = tiles of gathered 16-row groups (k_contract_spg), 128 = aligned row blocks (k_contract_sp),
                              // -1 = auto: 16 wherever 32-bit offsets address the inverse (Mp * Mp * 8 < 2^32)
-  // second set (with Bt2): the launches of the range-aware contraction alternate between two lanes on two streams, so that the
-  // candidate / right-hand-side / list kernels of one launch and the tail of the previous launch's tile queue overlap
-  DevBuf sp2_cand, sp2_flags, sp2_klist, sp2_kcount, sp2_nrows, sp2_rows, sp2_rstart, sp2_tiles, sp2_xoff, part2, queue2, sp2_recs;
+  PredictLane lane[2];
   int opt_sparse_lanes = 2;  // "sparse_lanes": 2 = two lanes (default since round 5), 1 = one launch after the other on one stream.  Round 4
                              // (profiles/r04_sparse_lanes_ab.txt): config-5 slab 64.6 -> 63.4 ms, 2 % for a second 8.4 GB panel: off.  Round 5, with
                              // the contraction 15 % shorter, what runs beside it weighs more: prediction 43.1 -> 41.6 ms (bench 35.3 -> 36.3 M points/s)
@@ -353,7 +364,7 @@ struct mik_handle {
   DevBuf px, py, pz, extra_rows, z, ss;
   DevBuf grid_axes, grid_idx;  // mik_set_grid: the axes and (masked style) the slab's compacted cell numbers
   // work
-  DevBuf Bt, Bt2, part, mw_idx, mw_dist, stat_S, stat_x, stat_out, queue;
+  DevBuf mw_idx, mw_dist, stat_S, stat_x, stat_out;
   int n_cu = 256;
   int t_state = 0;  // what T holds: 0 nothing, 1 the kriging matrix A (shift 0), 2 its inverse
   // options
@@ -372,14 +383,11 @@ struct mik_handle {
   int opt_mw_class = 0;       // 100 G + RI: force one thread-grid / register-tile class of k_mw_chol (0 = by window size)
   mik_timing tm{};
   std::vector<hipEvent_t> evpool;
-  std::vector<hipEvent_t> pr_events;  // predict: per chunk "right-hand sides written" / "contraction done" (two RHS panels)
+  std::vector<LaunchEvents> pr_launch;  // predict: the events of every launch
+  hipEvent_t ev_predict0 = nullptr, ev_predict1 = nullptr;  // predict: around the whole predict (timed; the second lane starts at ev_predict0)
+  hipEvent_t ev_lane1 = nullptr;      // predict, two lanes: lane 1's latest launch (the handle's stream joins it at the end)
   hipEvent_t ev_sort = nullptr;       // predict: the points of every launch are in order (k_ps_*: timed, and the second lane waits for it)
   hipEvent_t ev_chunk = nullptr;      // predict: chunk finished on the compute stream (the result copies wait for it)
-  // "rhs_overlap": k_rhs of the next chunk on a second stream while the current chunk is contracted (two RHS panels).
-  // Measured (profiles/r03_chunk_and_rhs_overlap_sweep_c2.txt): it does run concurrently -- and the contraction slows down by
-  // exactly the time k_rhs takes (362.8 + 9.1 ms serial = 372.6 ms per 10^6 points; 372.8 ms overlapped): fp64 VALU / HBM-write
-  // work does not hide under fp64 MFMAs on this part.  Off by default; kept as an option for the record.
-  int opt_rhs_overlap = 0;
   // comm
   ncclComm_t comm = nullptr;
   int nranks = 1, rank = 0;
@@ -490,7 +498,6 @@ int launch_mirror_upper(double* T, long Mp, hipStream_t st);                    
 int one_factor(mik_handle* h);                                                                                   // mik_inverse.hip
 int sort_points(mik_handle* h, long chunk, long nchunks);                                                        // mik_predict.hip
 int one_predict(mik_handle* h);                                                                                  // mik_predict.hip
-int fields_coefficients(mik_handle* h);                                                                          // mik_predict.hip
 int one_predict_mw(mik_handle* h, int n_closest);
 // mik_mw_chol.hip, part N: launches class 100 G + RI of k_mw_chol if it holds it, else returns MIK_MWC_NOCLASS
 #define MIK_MWC_PARTS 5

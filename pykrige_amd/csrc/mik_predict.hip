@@ -3,8 +3,6 @@
 #include "mik_k_predict.h"
 #include "mik_host.h"
 
-// Hilbert-curve order of the resident points inside every launch of `chunk` points (k_ps_*, mik_kernels.h): ps_idx[0][s] = index of
-// the point at sorted position s.  On the handle's stream; two radix passes of 10-bit digits, all segments side by side.
 // unit vectors of the resident (geographic) points, gu[0 .. npt) x, [npt .. 2 npt) y, [2 npt .. 3 npt) z; on the handle's stream
 static int geo_point_vectors(mik_handle* h) {
   const long npt = h->npt;
@@ -15,6 +13,8 @@ static int geo_point_vectors(mik_handle* h) {
   return MIK_OK;
 }
 
+// Hilbert-curve order of the resident points inside every launch of `chunk` points (k_ps_*, mik_kernels.h): ps_idx[0][s] = index of
+// the point at sorted position s.  On the handle's stream; two radix passes of 10-bit digits, all segments side by side.
 int sort_points(mik_handle* h, long chunk, long nchunks) {
   const long npt = h->npt;
   const int kd = h->ndim;  // (geographic points: the curve runs through (lon, lat), like the stations' -- mikrige.hip, station_order)
@@ -47,8 +47,8 @@ int sort_points(mik_handle* h, long chunk, long nchunks) {
 
 // Several value fields (mik_set_fields): C = A_inv[:, :N] V from this device's own copy of the inverse, MIK_FB columns per block of
 // k_cvec<MIK_FB> (column f is bit for bit the k_cvec of field f).  V goes up once per set of fields and station order.
-int fields_coefficients(mik_handle* h) {
-  // columns: a multiple of MIK_FB that also holds the last read-back launch's (fields 1 + MIK_FB k .. MIK_FB (k + 1), see one_predict)
+static int fields_coefficients(mik_handle* h) {
+  // columns: a multiple of MIK_FB that also holds the last read-back launch's (fields 1 + MIK_FB k .. MIK_FB (k + 1), see launch_rhs)
   const int nf = h->nf, nfp = ((nf - 1 + MIK_FB - 1) / MIK_FB) * MIK_FB + MIK_FB;
   const long N = h->N;
   const int want = h->factor_sorted ? 1 : 0;
@@ -76,25 +76,33 @@ int fields_coefficients(mik_handle* h) {
   return MIK_OK;
 }
 
-int one_predict(mik_handle* h) {
-  if (!h || !h->have_factor) return fail(MIK_ESTATE, "mik_predict: factor first");
-  if (!h->have_points) return fail(MIK_ESTATE, "mik_predict: set points first");
-  HIPC(hipSetDevice(h->device));
+// point blocks per group of k_sp_tiles_g's queue order (a group's tiles run on one XCD, tile position ascending, point block fast;
+// round 5: 4 -> 16, contraction 35.7 -> 35.3 ms at config 5)
+static constexpr int SP_GROUP = 16;
+
+// what one predict runs (plan_predict): launches of `chunk` points on the dense or the range-aware path, on one lane or two
+struct Plan {
+  long npt, chunk, nchunks;
+  int Mp, nIblk, nK16, nKt, kend, nf;
+  bool sparse, gathered, sortpts, lanes2;
+  const unsigned* perm;  // the points of every launch in Hilbert-curve order: ps_idx[0] (else nullptr)
+};
+
+// launch c of a plan: points [t0, t0 + nvalid), padded to palloc = 128 nTb
+struct Launch {
+  long c, t0;
+  int nvalid, palloc, nTb;
+  Launch(const Plan& p, long c_)
+      : c(c_), t0(c_ * p.chunk), nvalid((int)std::min<long>(p.chunk, p.npt - t0)), palloc(((nvalid + 127) / 128) * 128), nTb(palloc / 128) {}
+};
+
+// chunk size and count, path, lanes and point sort of this predict; the timing fields that describe them; the work buffers and events
+static int plan_predict(mik_handle* h, Plan& p) {
   const long npt = h->npt;
-  const int Mp = h->Mp, nIblk = Mp / 128;
-  h->tm.rhs_ms = h->tm.contract_ms = h->tm.predict_ms = 0.0;
-  h->tm.contract_launches = 0;
-  h->tm.contract_flops_executed = 0.0;
-  h->tm.symmetric = h->opt_sym;
-  h->tm.engine = 0;  // (the v_fma_f64 contraction left the library in round 6: tools/kernel_bench)
-  h->tm.mw_kernel = 0;
-  const int nf = h->nf;  // value fields (mik_set_fields): field 0 goes to z, the others to the planes of zf
-  h->nf_done = nf;
-  if (npt == 0) {
-    h->have_results = true;
-    return MIK_OK;
-  }
-  if (nf > 1) {
+  const int Mp = h->Mp, nIblk = Mp / 128, nf = h->nf;
+  p.npt = npt, p.Mp = Mp, p.nIblk = nIblk, p.nK16 = Mp / 16, p.nf = nf;
+  p.kend = ((h->M + MIK_BK - 1) / MIK_BK) * MIK_BK;
+  if (nf > 1) {  // value fields (mik_set_fields): field 0 goes to z, the others to the planes of zf
     MIKC(h->zf.ensure(sizeof(double) * (size_t)(nf - 1) * (size_t)npt));
     // page-locked landing zone of fields 1 .. nf - 1, filled chunk by chunk like pin_out (an earlier predict's copies may still write it)
     HIPC(hipEventSynchronize(h->ev_d2h));
@@ -103,424 +111,412 @@ int one_predict(mik_handle* h) {
   long chunk = std::min<long>(h->opt_chunk, ((npt + 127) / 128) * 128);
   if (h->model == MIK_MODEL_CUSTOM) chunk = std::min<long>(chunk, 16384);  // each chunk's distances visit the host
   // range-aware contraction (k_contract_sp): the factor is in Hilbert-curve station order and the variogram has compact support
-  const bool sparse = h->factor_sorted && h->opt_sparse != 2 && h->opt_sparse != 0;
-  if (sparse) chunk = std::min<long>(chunk, 131072);  // k_sp_tiles: at most 1024 point blocks per launch
-  const int nK16 = Mp / 16;
+  p.sparse = h->factor_sorted && h->opt_sparse != 2 && h->opt_sparse != 0;
+  if (p.sparse) chunk = std::min<long>(chunk, 131072);  // k_sp_tiles: at most 1024 point blocks per launch
   // tiles of gathered 16-row groups (k_contract_spg) wherever 32-bit LDS-DMA offsets reach every row of the inverse
-  const bool gathered = sparse && h->opt_sparse_rows != 128 && (double)Mp * (double)Mp * 8.0 < 4294967296.0;
+  p.gathered = p.sparse && h->opt_sparse_rows != 128 && (double)Mp * (double)Mp * 8.0 < 4294967296.0;
   // gathered row groups (round 5): flags and lists per 8 stations (candidates stay per 16), a K step = a pair of list-adjacent 8-station tiles
   // (k_contract_spg H8); the aligned-block fallback keeps 16-station lists.  nKt = tiles per point block in the units of this launch's lists.
   // (Round 4's 16-station lists under gathered groups and the epilogue from global memory -- "sparse_ktile" 16, "sparse_epilogue" 0 -- lost
   // their A/B in round 5 and left the library in round 6.)
-  const bool h8 = gathered;
-  const int nKt = h8 ? Mp / 8 : nK16;
-  h->tm.sparse_ktile = !sparse ? 0 : h8 ? 8 : 16;
-  h->tm.sparse = sparse ? 1 : 0;
-  h->tm.sparse_rows = sparse ? (gathered ? 16 : 128) : 0;
+  p.nKt = p.gathered ? Mp / 8 : p.nK16;
+  h->tm.sparse_ktile = !p.sparse ? 0 : p.gathered ? 8 : 16;
+  h->tm.sparse = p.sparse ? 1 : 0;
+  h->tm.sparse_rows = p.sparse ? (p.gathered ? 16 : 128) : 0;
   h->tm.stations_sorted = h->factor_sorted ? 1 : 0;
   h->tm.sparse_tiles = h->tm.sparse_tiles_dense = h->tm.sparse_ktiles = h->tm.sparse_ktiles_dense = h->tm.sparse_lists_ms = 0.0;
   h->tm.sparse_diag_products = 0.0;
   // the points of every launch in Hilbert-curve order among themselves (compact point blocks: option "sort_points")
   // (auto: not for small jobs -- seven more launches, 0.07 ms, against a contraction of microseconds; one tile per point block anyway
   // while the matrix has fewer than 512 rows)
-  const bool sortpts = sparse && (h->opt_sort_points == 1 || (h->opt_sort_points < 0 && npt >= 4096 && Mp >= 512));
-  h->tm.points_sorted = sortpts ? 1 : 0;
+  p.sortpts = p.sparse && (h->opt_sort_points == 1 || (h->opt_sort_points < 0 && npt >= 4096 && Mp >= 512));
+  h->tm.points_sorted = p.sortpts ? 1 : 0;
   h->tm.sort_points_ms = 0.0;
-  // "rhs_overlap" (off by default, see the option): two RHS panels, k_rhs of chunk c + 1 on a second stream while chunk c is
-  // contracted.
-  const bool overlap = h->opt_rhs_overlap && h->model != MIK_MODEL_CUSTOM && !sparse;
-  const bool lanes2_wanted = sparse && h->opt_sparse_lanes == 2;
+  const bool lanes2_wanted = p.sparse && h->opt_sparse_lanes == 2;
   // keep the RHS panels under ~1/4 of device memory
   size_t freeb = 0, totalb = 0;
   HIPC(hipMemGetInfo(&freeb, &totalb));
-  const size_t have = h->Bt.bytes + h->Bt2.bytes;
-  while (chunk > 128 && (size_t)chunk * Mp * sizeof(double) * ((overlap || lanes2_wanted) ? 2 : 1) > std::max(freeb + have, have) / 2) chunk = ((chunk / 2 + 127) / 128) * 128;
+  const size_t have = h->lane[0].Bt.bytes + h->lane[1].Bt.bytes;
+  while (chunk > 128 && (size_t)chunk * Mp * sizeof(double) * (lanes2_wanted ? 2 : 1) > std::max(freeb + have, have) / 2) chunk = ((chunk / 2 + 127) / 128) * 128;
   // equal chunks: ceil(npt / chunk) launches of the same size (a short last launch drains as long as a full one)
   long nchunks = (npt + chunk - 1) / chunk;
   chunk = (((npt + nchunks - 1) / nchunks + 127) / 128) * 128;
   nchunks = (npt + chunk - 1) / chunk;
-  MIKC(h->Bt.ensure(sizeof(double) * (size_t)chunk * Mp));
-  if (overlap && nchunks > 1) MIKC(h->Bt2.ensure(sizeof(double) * (size_t)chunk * Mp));
-  const bool two = overlap && nchunks > 1;
-  MIKC(h->part.ensure(sizeof(double) * (size_t)chunk * nIblk));
+  p.chunk = chunk, p.nchunks = nchunks;
+  p.lanes2 = lanes2_wanted && nchunks > 1;
   MIKC(h->pin_out.ensure(sizeof(double) * 2 * (size_t)npt));  // (a previous result may have left with mik_take_results)
-  MIKC(get_events(h, 2 + 6 * (size_t)nchunks));
-  std::vector<unsigned long long> sp_host;
-  const bool lanes2 = lanes2_wanted && nchunks > 1;
-  struct SpLane {
-    DevBuf *cand, *flags, *klist, *kcount, *nrows, *rows, *rstart, *tiles, *xoff, *part, *queue, *Bt, *recs;
-    hipStream_t st;
-  };
-  SpLane lane[2] = {{&h->sp_cand, &h->sp_flags, &h->sp_klist, &h->sp_kcount, &h->sp_nrows, &h->sp_rows, &h->sp_rstart, &h->sp_tiles, &h->sp_xoff,
-                     &h->part, &h->queue, &h->Bt, &h->sp_recs, h->stream},
-                    {&h->sp2_cand, &h->sp2_flags, &h->sp2_klist, &h->sp2_kcount, &h->sp2_nrows, &h->sp2_rows, &h->sp2_rstart, &h->sp2_tiles,
-                     &h->sp2_xoff, &h->part2, &h->queue2, &h->Bt2, &h->sp2_recs, h->stream2}};
-  if (sparse) {
-    const size_t nTb = (size_t)chunk / 128;
-    for (int L = 0; L < (lanes2 ? 2 : 1); ++L) {
-      MIKC(lane[L].cand->ensure(nTb * nK16));
-      MIKC(lane[L].flags->ensure(nTb * nKt));
-      MIKC(lane[L].klist->ensure(sizeof(unsigned short) * nTb * nKt));
-      MIKC(lane[L].kcount->ensure(sizeof(int) * nTb));
-      MIKC(lane[L].nrows->ensure(sizeof(int) * nTb));
-      if (gathered) {
-        MIKC(lane[L].recs->ensure((h8 ? 48 : 32) * nTb * nIblk));  // ceil(nk / 8) <= nK16 / 8 = nIblk tiles per point block
-      } else {
-        MIKC(lane[L].rows->ensure(sizeof(unsigned short) * nTb * nIblk));
-        MIKC(lane[L].rstart->ensure(sizeof(unsigned short) * nTb * nIblk));
-        MIKC(lane[L].tiles->ensure(sizeof(unsigned) * nTb * nIblk));
-      }
-      MIKC(lane[L].xoff->ensure(sizeof(int) * 9));
-      MIKC(lane[L].queue->ensure(8 * sizeof(unsigned long long)));
-      if (L == 1) {
-        MIKC(h->Bt2.ensure(sizeof(double) * (size_t)chunk * Mp));
-        MIKC(h->part2.ensure(sizeof(double) * (size_t)chunk * nIblk));
-      }
+  if ((long)h->pr_launch.size() < nchunks) h->pr_launch.resize((size_t)nchunks);
+  for (LaunchEvents& ev : h->pr_launch)
+    for (hipEvent_t* e : ev.all())
+      if (!*e) HIPC(hipEventCreate(e));
+  const size_t nTb = (size_t)chunk / 128;
+  for (int L = 0; L < (p.lanes2 ? 2 : 1); ++L) {
+    PredictLane& ln = h->lane[L];
+    MIKC(ln.Bt.ensure(sizeof(double) * (size_t)chunk * Mp));
+    MIKC(ln.part.ensure(sizeof(double) * (size_t)chunk * nIblk));
+    MIKC(ln.queue.ensure(8 * sizeof(unsigned long long)));
+    if (!p.sparse) break;
+    MIKC(ln.cand.ensure(nTb * p.nK16));
+    MIKC(ln.flags.ensure(nTb * p.nKt));
+    MIKC(ln.klist.ensure(sizeof(unsigned short) * nTb * p.nKt));
+    MIKC(ln.kcount.ensure(sizeof(int) * nTb));
+    MIKC(ln.nrows.ensure(sizeof(int) * nTb));
+    if (p.gathered) {
+      MIKC(ln.recs.ensure(48 * nTb * nIblk));  // ceil(nk / 8) <= nK16 / 8 = nIblk tiles per point block
+    } else {
+      MIKC(ln.rows.ensure(sizeof(unsigned short) * nTb * nIblk));
+      MIKC(ln.rstart.ensure(sizeof(unsigned short) * nTb * nIblk));
+      MIKC(ln.tiles.ensure(sizeof(unsigned) * nTb * nIblk));
     }
-    MIKC(h->sp_stats.ensure(sizeof(unsigned long long) * 4 * (size_t)nchunks));
-    sp_host.assign(4 * (size_t)nchunks, 0ULL);
+    MIKC(ln.xoff.ensure(sizeof(int) * 9));
   }
-  while (h->pr_events.size() < 2 * (size_t)nchunks) {
-    hipEvent_t e;
-    HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    h->pr_events.push_back(e);
+  if (p.sparse) MIKC(h->sp_stats.ensure(sizeof(unsigned long long) * 4 * (size_t)nchunks));
+  return MIK_OK;
+}
+
+// the right-hand sides of launch l into lane ln's panel on stream st, with z of every field; the range-aware path first marks the
+// candidate station tiles of every point block and then writes delta for those only
+static int launch_rhs(mik_handle* h, const Plan& p, const Launch& l, PredictLane& ln, hipStream_t st) {
+  const LaunchEvents& ev = h->pr_launch[(size_t)l.c];
+  const long t0 = l.t0, npt = p.npt;
+  RhsArgs a{};
+  a.Bt = ln.Bt.as<double>();
+  a.ld = p.Mp;
+  a.palloc = l.palloc;
+  a.nvalid = l.nvalid;
+  a.px = h->px.as<double>() + t0;
+  a.py = h->py.as<double>() + t0;
+  a.pz = h->ndim == 3 ? h->pz.as<double>() + t0 : nullptr;
+  a.N = h->N;
+  a.p = h->p;
+  a.M = h->M;
+  a.Mp = p.Mp;
+  a.ndim = h->ndim;
+  a.xs = h->factor_sorted ? h->xs_s.as<double>() : h->xs.as<double>();
+  a.ys = h->factor_sorted ? h->ys_s.as<double>() : h->ys.as<double>();
+  a.zs = h->factor_sorted ? h->zs_s.as<double>() : h->zs.as<double>();
+  a.dsc = h->factor_eq ? h->dsc.as<double>() : nullptr;
+  a.v = h->v;
+  a.exact = h->exact;
+  a.eps = h->eps;
+  a.rl = h->rl;
+  a.nwells = h->nwells;
+  a.nextra = h->nextra;
+  a.wells = h->wells.as<double>();
+  a.extra = h->nextra ? h->extra_rows.as<double>() + t0 : nullptr;
+  a.extra_stride = npt;
+  a.cvec = p.nf > 0 ? (const double*)h->fc.as<double>() : (const double*)h->cvec.as<double>();
+  a.zout = h->z.as<double>() + t0;
+  const dim3 grid(l.palloc / MIK_TP), block(256);
+  if (!p.sparse) {
+    HIPC(hipEventRecord(ev.rhs_begin, st));
+    if (h->model == MIK_MODEL_CUSTOM) {
+      DISPATCH_NDIM_FIXED(7, h->geo ? 1 : h->ndim, k_rhs, grid, block, st, a);
+      MIKC(custom_roundtrip(h, a.Bt, l.nvalid, h->N, p.Mp));
+      DISPATCH_NDIM_FIXED(6, h->geo ? 1 : h->ndim, k_rhs, grid, block, st, a);
+    } else {
+      DISPATCH_MODEL_NDIM(h->model, h->geo ? 1 : h->ndim, k_rhs, grid, block, st, a);
+    }
+  } else {  // candidates (bounding boxes), cleared flags, then delta for the candidate blocks only
+    a.cand = ln.cand.as<unsigned char>();
+    a.flags = ln.flags.as<unsigned char>();
+    a.nIblk = p.nIblk;
+    a.nK16 = p.nK16;
+    a.nKf = p.nKt;
+    a.sill = h->v.p0 + h->v.p2;
+    if (p.perm) {  // sorted order: the chunk's points are reached through perm, from the list's base pointers
+      a.perm = p.perm + t0;
+      a.px = h->px.as<double>();
+      a.py = h->py.as<double>();
+      a.pz = h->ndim == 3 ? h->pz.as<double>() : nullptr;
+      a.extra = h->nextra ? h->extra_rows.as<double>() : nullptr;
+      a.zout = h->z.as<double>();
+    }
+    HIPC(hipEventRecord(ev.cand_begin, st));
+    // candidates by bounding boxes: Euclidean coordinates against the range; geographic: unit vectors against the CHORD of the range
+    // (2 sin(arc / 2), the range being degrees of arc; beyond 180 degrees everything is in range)
+    const double *cx = a.px, *cy = a.py, *cz = a.pz;
+    double radius = std::max(h->v.p1, h->eps);
+    if (h->geo) {
+      const long off = p.perm ? 0 : t0;
+      cx = h->gu.as<double>() + off, cy = cx + npt, cz = cy + npt;
+      radius = radius >= 180.0 ? 4.0 : 2.0 * std::sin(radius * 3.14159265358979323846 / 360.0) * (1.0 + 1e-12) + 1e-15;
+    }
+    hipLaunchKernelGGL(k_sp_cand, dim3(l.palloc / 128), dim3(128), 0, st, cx, cy, cz, l.nvalid, (const double*)h->sbox.as<double>(), p.nK16,
+                       h->N / 16, (h->M + 15) / 16, radius, ln.cand.as<unsigned char>(), a.perm, p.gathered ? 0 : 1, ln.flags.as<unsigned char>(), p.nKt);
+    HIPC(hipEventRecord(ev.rhs_begin, st));
+    if (p.gathered) {
+      if (h->geo) hipLaunchKernelGGL((k_rhs<3, 1, true, true>), grid, block, 0, st, a);
+      else if (h->ndim == 3) hipLaunchKernelGGL((k_rhs<3, 3, true, true>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((k_rhs<3, 2, true, true>), grid, block, 0, st, a);
+    } else if (h->geo) hipLaunchKernelGGL((k_rhs<3, 1, true>), grid, block, 0, st, a);
+    else if (h->ndim == 3) hipLaunchKernelGGL((k_rhs<3, 3, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_rhs<3, 2, true>), grid, block, 0, st, a);
   }
-  const int kend = ((h->M + MIK_BK - 1) / MIK_BK) * MIK_BK;
-  hipStream_t sc = h->stream;                  // contraction, reduction
-  hipStream_t sr = two ? h->stream2 : h->stream;  // right-hand sides
+  // fields 1 .. nf - 1: MIK_FB per launch, read back from the panel the launch of field 0 has just written (same stream, right after it)
+  for (int f0 = 1; f0 < p.nf; f0 += MIK_FB) {
+    RhsArgs b = a;
+    b.cvec = h->fc.as<double>() + (size_t)f0 * p.Mp;
+    b.cf_ld = p.Mp;
+    b.nfc = std::min(MIK_FB, p.nf - f0);
+    b.zout = h->zf.as<double>() + (size_t)(f0 - 1) * npt + (b.perm ? 0 : t0);
+    b.zf_ld = npt;
+    if (p.sparse) hipLaunchKernelGGL((k_rhs<0, 0, true, false, MIK_FB>), grid, block, 0, st, b);
+    else hipLaunchKernelGGL((k_rhs<0, 0, false, false, MIK_FB>), grid, block, 0, st, b);
+  }
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(ev.rhs_end, st));
+  return MIK_OK;
+}
+
+// dense contraction of launch l on the handle's stream with lane 0's buffers: row-block partial sums of b^T A_inv b, reduced to sigma^2
+static int contract_dense(mik_handle* h, const Plan& p, const Launch& l) {
+  const LaunchEvents& ev = h->pr_launch[(size_t)l.c];
+  PredictLane& ln = h->lane[0];
+  hipStream_t sc = h->stream;
+  const int nIblk = p.nIblk, kend = p.kend;
+  HIPC(hipEventRecord(ev.contract_begin, sc));
+  const double* Ai = h->T.as<double>();
+  const double* Bi = ln.Bt.as<double>();
+  double* pp = ln.part.as<double>();
+  const long ldm = p.Mp;
+  const unsigned sgrid = (unsigned)super_grid(nIblk, l.nTb);
+  // persistent launch: 2 blocks per CU pop tiles from per-XCD sequences (8 counters, zeroed per launch); 8 wavefronts per tile
+  // (wave tile 32 x 64).  Three forms: the symmetric half product with triangular diagonal blocks (default), with whole
+  // diagonal blocks ("tri" 0) and the reference's full product w = A_inv b ("symmetric" 0) -- the cross-checks of the parity tests.
+  // (The 4-wave tiles, the v_fma_f64 engine, pair units, popped-ahead tiles: every A/B of rounds 2-5 lost; tools/kernel_bench.)
+  HIPC(hipMemsetAsync(ln.queue.p, 0, 8 * sizeof(unsigned long long), sc));
+  unsigned long long* qp = ln.queue.as<unsigned long long>();
+  const unsigned pgrid = (unsigned)std::min<long>(2L * h->n_cu, (long)sgrid);
+  if (h->opt_sym && h->opt_tri) hipLaunchKernelGGL((k_contract<true, 2, true, false, true>), dim3(pgrid), dim3(512), 0, sc, Ai, ldm, Bi, ldm, pp, l.palloc, nIblk, kend, qp);
+  else if (h->opt_sym) hipLaunchKernelGGL((k_contract<true, 2>), dim3(pgrid), dim3(512), 0, sc, Ai, ldm, Bi, ldm, pp, l.palloc, nIblk, kend, qp);
+  else hipLaunchKernelGGL((k_contract<false, 2>), dim3(pgrid), dim3(512), 0, sc, Ai, ldm, Bi, ldm, pp, l.palloc, nIblk, kend, qp);
+  HIPC(hipEventRecord(ev.contract_end, sc));
+  hipLaunchKernelGGL(k_ss_reduce, dim3((l.nvalid + 255) / 256), dim3(256), 0, sc, (const double*)pp, l.palloc, nIblk, l.nvalid,
+                     h->ss.as<double>() + l.t0);
+  return MIK_OK;
+}
+
+// diagnostic (MIK_SPG_PROF=1): the contraction of one launch in k_contract_spg's profiling instantiation; cycle sums per phase of the
+// tile loop, printed to stderr
+static int spg_profile(SpgArgs ga, unsigned nb, hipStream_t sc) {
+  static DevBuf pb;
+  MIKC(pb.ensure(sizeof(unsigned long long) * nb * 96));
+  HIPC(hipMemsetAsync(pb.p, 0, pb.bytes, sc));
+  ga.prof = pb.as<unsigned long long>();
+  hipLaunchKernelGGL((k_contract_spg<2, true, true, true>), dim3(nb), dim3(512), 0, sc, ga);
+  std::vector<unsigned long long> hp((size_t)nb * 96);
+  HIPC(hipMemcpyAsync(hp.data(), pb.p, sizeof(unsigned long long) * hp.size(), hipMemcpyDeviceToHost, sc));
+  HIPC(hipStreamSynchronize(sc));
+  static const char* names[8] = {"top drain+barrier", "off-diagonal K steps", "triangle K steps", "acquire", "adopt", "epilogue loads+sums", "reduce+store", "-"};
+  {
+    double c[16] = {0};
+    for (unsigned b = 0; b < nb; ++b)
+      for (int i = 0; i < 16; ++i) c[i] += (double)hp[(size_t)nb * 80 + (size_t)b * 16 + i];
+    fprintf(stderr, "spg triangle steps (cycles per visit):");
+    for (int w = 7; w >= 0; --w) fprintf(stderr, "  w=%d %.0f", w, c[w] / std::max(1.0, c[8 + w]));
+    fprintf(stderr, "\n");
+  }
+  for (int wv : {0, 6}) {
+    double sum[10] = {0};
+    for (unsigned b = 0; b < nb; ++b)
+      for (int i = 0; i < 10; ++i) sum[i] += (double)hp[((size_t)b * 8 + wv) * 10 + i];
+    double tot = 0;
+    for (int i = 0; i < 7; ++i) tot += sum[i];
+    fprintf(stderr, "spg phases, wavefront %d: %.0f tiles of the launch, %.1f per block, %.1f off-diagonal steps per tile, %.0f cycles per tile\n", wv, sum[8], sum[8] / nb, sum[9] / std::max(1.0, sum[8]), tot / std::max(1.0, sum[8]));
+    for (int i = 0; i < 7; ++i) fprintf(stderr, "   %-22s %8.0f cycles per tile  %5.1f %%\n", names[i], sum[i] / std::max(1.0, sum[8]), 100.0 * sum[i] / tot);
+    fprintf(stderr, "   per off-diagonal step %.0f cycles\n", sum[1] / std::max(1.0, sum[9]));
+  }
+  return MIK_OK;
+}
+
+// range-aware launch l on lane ln (stream sc): the lists of active K tiles and the tile records / sequences, the contraction of the
+// active tiles, sigma^2
+static int contract_sparse(mik_handle* h, const Plan& p, const Launch& l, PredictLane& ln, hipStream_t sc) {
+  const LaunchEvents& ev = h->pr_launch[(size_t)l.c];
+  const int nTb = l.nTb, nIblk = p.nIblk;
+  unsigned long long* stats = h->sp_stats.as<unsigned long long>() + 4 * l.c;
+  if (p.gathered) {
+    hipLaunchKernelGGL(k_sp_lists_g, dim3(nTb), dim3(64), 0, sc, (const unsigned char*)ln.flags.as<unsigned char>(), p.nKt,
+                       ln.klist.as<unsigned short>(), ln.kcount.as<int>(), ln.nrows.as<int>(), 1);
+    hipLaunchKernelGGL(k_sp_tiles_g<true>, dim3((unsigned)((nTb + SP_GROUP - 1) / SP_GROUP)), dim3(256), 0, sc, (const int*)ln.nrows.as<int>(),
+                       (const int*)ln.kcount.as<int>(), (const unsigned short*)ln.klist.as<unsigned short>(), p.nKt, nTb, ln.recs.as<uint4>(),
+                       ln.xoff.as<int>(), stats, SP_GROUP, ln.queue.as<unsigned long long>());
+  } else {
+    hipLaunchKernelGGL(k_sp_lists, dim3(nTb), dim3(64), 0, sc, (const unsigned char*)ln.flags.as<unsigned char>(), p.nK16, nIblk,
+                       ln.klist.as<unsigned short>(), ln.kcount.as<int>(), ln.rows.as<unsigned short>(), ln.rstart.as<unsigned short>(),
+                       ln.nrows.as<int>());
+    hipLaunchKernelGGL(k_sp_tiles, dim3(1), dim3(1024), 0, sc, (const int*)ln.nrows.as<int>(), (const int*)ln.kcount.as<int>(),
+                       (const unsigned short*)ln.rstart.as<unsigned short>(), nIblk, nTb, ln.tiles.as<unsigned>(), ln.xoff.as<int>(), stats);
+  }
+  HIPC(hipEventRecord(ev.lists_end, sc));
+  if (!p.gathered) HIPC(hipMemsetAsync(ln.queue.p, 0, 8 * sizeof(unsigned long long), sc));  // (gathered: k_sp_tiles_g zeroes the queues)
+  // two lanes: the CONTRACTIONS run one after the other (this one behind the other lane's previous one); what overlaps a contraction is the
+  // other lane's candidate / right-hand-side / list kernels in its tail.  Two persistent launches side by side share every CU and mix two
+  // tile queues in every XCD's L2: measured 3.5 % slower per pair (profiles/r06_predict_timeline_c5.txt; rounds 4-5 got this order by accident:
+  // the queue memset in front of the contraction waited for a free CU).
+  if (p.lanes2 && l.c > 0) HIPC(hipStreamWaitEvent(sc, h->pr_launch[(size_t)l.c - 1].contract_end, 0));
+  HIPC(hipEventRecord(ev.contract_begin, sc));
+  // (2 n_cu persistent blocks: leaving 32 .. 128 of the slots to the other lane's preparation kernels was tried -- they then run beside the
+  // contraction at a fraction of the chip -- and measured a tie at 32 and 1 - 3 % slower beyond: profiles/r06_predict_timeline_c5_after.txt)
+  const unsigned nb = (unsigned)std::min<long>(2L * h->n_cu, (long)nTb * nIblk);
+  if (p.gathered) {
+    SpgArgs ga{};
+    ga.Ainv = h->T.as<double>();
+    ga.lda = p.Mp;
+    ga.Bt = ln.Bt.as<double>();
+    ga.ldb = p.Mp;
+    ga.part = ln.part.as<double>();
+    ga.palloc = l.palloc;
+    ga.nK16 = p.nKt;
+    ga.klist = ln.klist.as<unsigned short>();
+    ga.recs = ln.recs.as<uint4>();
+    ga.xoff = ln.xoff.as<int>();
+    ga.queue = ln.queue.as<unsigned long long>();
+    static const bool spg_prof = getenv("MIK_SPG_PROF") && atoi(getenv("MIK_SPG_PROF")) != 0;
+    if (spg_prof) MIKC(spg_profile(ga, nb, sc));
+    else hipLaunchKernelGGL((k_contract_spg<2, true, true>), dim3(nb), dim3(512), 0, sc, ga);
+  } else {
+    SpArgs sa{};
+    sa.Ainv = h->T.as<double>();
+    sa.lda = p.Mp;
+    sa.Bt = ln.Bt.as<double>();
+    sa.ldb = p.Mp;
+    sa.part = ln.part.as<double>();
+    sa.palloc = l.palloc;
+    sa.kend = p.kend;
+    sa.nIblk = nIblk;
+    sa.nK16 = p.nK16;
+    sa.klist = ln.klist.as<unsigned short>();
+    sa.kcount = ln.kcount.as<int>();
+    sa.rows = ln.rows.as<unsigned short>();
+    sa.rstart = ln.rstart.as<unsigned short>();
+    sa.tiles = ln.tiles.as<unsigned>();
+    sa.xoff = ln.xoff.as<int>();
+    sa.queue = ln.queue.as<unsigned long long>();
+    hipLaunchKernelGGL((k_contract_sp<2>), dim3(nb), dim3(512), 0, sc, sa);
+  }
+  HIPC(hipEventRecord(ev.contract_end, sc));
+  hipLaunchKernelGGL(k_ss_reduce_sp, dim3((l.nvalid + 255) / 256), dim3(256), 0, sc, (const double*)ln.part.as<double>(), l.palloc,
+                     (const int*)ln.nrows.as<int>(), l.nvalid, 2.0 * (h->v.p0 + h->v.p2),
+                     p.perm ? h->ss.as<double>() : h->ss.as<double>() + l.t0, p.perm ? p.perm + l.t0 : (const unsigned*)nullptr);
+  if (p.lanes2 && (l.c & 1)) HIPC(hipEventRecord(h->ev_lane1, sc));  // lane 1's latest launch (joined at the end of the predict)
+  return MIK_OK;
+}
+
+// launch l's z and sigma^2, and z of fields 1 .. nf - 1, leave for the page-locked landing zones while the next launch is computed (on
+// stream_d2h, behind ev_chunk on the launch's stream st)
+static int copy_out(mik_handle* h, const Plan& p, const Launch& l, hipStream_t st) {
+  const size_t bytes = sizeof(double) * l.nvalid;
+  HIPC(hipEventRecord(h->ev_chunk, st));
+  HIPC(hipStreamWaitEvent(h->stream_d2h, h->ev_chunk, 0));
+  HIPC(hipMemcpyAsync(h->pin_out.as<double>() + l.t0, h->z.as<double>() + l.t0, bytes, hipMemcpyDeviceToHost, h->stream_d2h));
+  HIPC(hipMemcpyAsync(h->pin_out.as<double>() + p.npt + l.t0, h->ss.as<double>() + l.t0, bytes, hipMemcpyDeviceToHost, h->stream_d2h));
+  for (int f = 1; f < p.nf; ++f)
+    HIPC(hipMemcpyAsync(h->pin_fz.as<double>() + (size_t)(f - 1) * p.npt + l.t0, h->zf.as<double>() + (size_t)(f - 1) * p.npt + l.t0, bytes,
+                        hipMemcpyDeviceToHost, h->stream_d2h));
+  return MIK_OK;
+}
+
+// after the handle's stream has finished: the event-timed durations, the range-aware path's tile counts, the executed flops
+static int read_back(mik_handle* h, const Plan& p, bool sorted_now) {
+  float ms = 0.f;
+  HIPC(hipEventElapsedTime(&ms, h->ev_predict0, h->ev_predict1));
+  h->tm.predict_ms = ms;
+  if (sorted_now) {
+    HIPC(hipEventElapsedTime(&ms, h->ev_predict0, h->ev_sort));
+    h->tm.sort_points_ms = ms;
+  }
+  std::vector<unsigned long long> sp(p.sparse ? 4 * (size_t)p.nchunks : 0);
+  if (p.sparse) HIPC(hipMemcpy(sp.data(), h->sp_stats.p, sizeof(unsigned long long) * sp.size(), hipMemcpyDeviceToHost));
+  // dense: executed flops of a launch: per tile 2*128*128*(k extent)
+  // (triangular diagonal blocks: nt (nt + 1) / 2 products of 16 rows x 16 k instead of 8 nt, nt = K tiles of the block)
+  const bool tri = h->opt_sym && h->opt_tri;
+  double kext = 0.0;
+  for (int ib = 0; ib < p.nIblk; ++ib) {
+    const int ext = h->opt_sym ? std::max(0, p.kend - ib * 128) : p.kend;
+    if (tri) {
+      const int nt = std::min(ext, 128) / 16;
+      kext += (ext - 16 * nt) + 16.0 * (nt * (nt + 1) / 2) / 8.0;
+    } else kext += ext;
+  }
+  const int ntl = (p.kend - (p.nIblk - 1) * 128) / 16;  // K tiles of the (short) last block
+  for (long c = 0; c < p.nchunks; ++c) {
+    const LaunchEvents& ev = h->pr_launch[(size_t)c];
+    const int nTb = Launch(p, c).nTb;
+    HIPC(hipEventElapsedTime(&ms, ev.rhs_begin, ev.rhs_end));
+    h->tm.rhs_ms += ms;
+    HIPC(hipEventElapsedTime(&ms, ev.contract_begin, ev.contract_end));
+    h->tm.contract_ms += ms;
+    if (!p.sparse) {
+      h->tm.contract_flops_executed += 2.0 * 128.0 * 128.0 * kext * nTb;
+      continue;
+    }
+    HIPC(hipEventElapsedTime(&ms, ev.cand_begin, ev.rhs_begin));
+    h->tm.sparse_lists_ms += ms;
+    HIPC(hipEventElapsedTime(&ms, ev.rhs_end, ev.lists_end));
+    h->tm.sparse_lists_ms += ms;
+    h->tm.sparse_tiles_dense += (double)nTb * p.nIblk;
+    h->tm.sparse_ktiles_dense += (double)nTb * (p.kend / 16.0) * (p.nIblk - 1) / 2.0;  // off-diagonal K tiles of the dense symmetric form (about)
+    const double tiles = (double)sp[4 * c], offk = (double)sp[4 * c + 1];
+    h->tm.sparse_tiles += tiles;
+    h->tm.sparse_ktiles += offk;
+    // executed flops: off-diagonal K tiles are 128 x 16 x 128 products; a diagonal block is nt (nt + 1) / 2 products of 16 rows x 16 k
+    // x 128 points (nt = 8, or the short last block's -- every point block has that row block: the last row is the 1 of ok.py:673;
+    // gathered groups: k_sp_tiles_g counted the products of the triangular parts, short last tiles included)
+    const double diagp = p.gathered ? (double)sp[4 * c + 2] : 36.0 * std::max(0.0, tiles - (double)nTb) + (ntl * (ntl + 1) / 2) * (double)nTb;
+    h->tm.sparse_diag_products += diagp;
+    h->tm.contract_flops_executed += 2.0 * 128.0 * 16.0 * 128.0 * offk + 2.0 * 16.0 * 16.0 * 128.0 * diagp;
+  }
+  h->tm.contract_launches = p.nchunks;
+  return MIK_OK;
+}
+
+int one_predict(mik_handle* h) {
+  if (!h || !h->have_factor) return fail(MIK_ESTATE, "mik_predict: factor first");
+  if (!h->have_points) return fail(MIK_ESTATE, "mik_predict: set points first");
+  HIPC(hipSetDevice(h->device));
+  h->tm.rhs_ms = h->tm.contract_ms = h->tm.predict_ms = 0.0;
+  h->tm.contract_launches = 0;
+  h->tm.contract_flops_executed = 0.0;
+  h->tm.symmetric = h->opt_sym;
+  h->tm.engine = 0;  // (the v_fma_f64 contraction left the library in round 6: tools/kernel_bench)
+  h->tm.mw_kernel = 0;
+  h->nf_done = h->nf;
+  if (h->npt == 0) {
+    h->have_results = true;
+    return MIK_OK;
+  }
+  Plan p{};
+  MIKC(plan_predict(h, p));
   HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));  // an earlier predict's result copies still read z / ss
-  if (sparse && h->geo) MIKC(geo_point_vectors(h));  // what the candidate boxes of a geographic problem are built from
-  // C of the fields first: the second stream (two right-hand-side panels, the second lane of the range-aware path) starts at evpool[0], and
-  // every k_rhs reads C
-  if (nf > 0) MIKC(fields_coefficients(h));
-  HIPC(hipEventRecord(h->evpool[0], h->stream));
+  if (p.sparse && h->geo) MIKC(geo_point_vectors(h));  // what the candidate boxes of a geographic problem are built from
+  // C of the fields first: the second lane starts at ev_predict0, and every k_rhs reads C
+  if (p.nf > 0) MIKC(fields_coefficients(h));
+  HIPC(hipEventRecord(h->ev_predict0, h->stream));
   bool sorted_now = false;
-  if (sortpts && !(h->ps_valid && h->ps_chunk == chunk)) {
-    MIKC(sort_points(h, chunk, nchunks));
+  if (p.sortpts && !(h->ps_valid && h->ps_chunk == p.chunk)) {
+    MIKC(sort_points(h, p.chunk, p.nchunks));
     HIPC(hipEventRecord(h->ev_sort, h->stream));
     sorted_now = true;
   }
-  const unsigned* perm_all = sortpts ? h->ps_idx[0].as<unsigned>() : nullptr;
-  if (two || lanes2) HIPC(hipStreamWaitEvent(h->stream2, h->evpool[0], 0));
-  if (lanes2 && sorted_now) HIPC(hipStreamWaitEvent(h->stream2, h->ev_sort, 0));
-  auto launch_rhs = [&](long c) -> int {
-    const long t0 = c * chunk;
-    const int nvalid = (int)std::min<long>(chunk, npt - t0);
-    const int palloc = ((nvalid + 127) / 128) * 128;
-    RhsArgs a{};
-    a.Bt = (two && (c & 1)) ? h->Bt2.as<double>() : h->Bt.as<double>();
-    a.ld = Mp;
-    a.palloc = palloc;
-    a.nvalid = nvalid;
-    a.px = h->px.as<double>() + t0;
-    a.py = h->py.as<double>() + t0;
-    a.pz = h->ndim == 3 ? h->pz.as<double>() + t0 : nullptr;
-    a.N = h->N;
-    a.p = h->p;
-    a.M = h->M;
-    a.Mp = Mp;
-    a.ndim = h->ndim;
-    a.xs = h->factor_sorted ? h->xs_s.as<double>() : h->xs.as<double>();
-    a.ys = h->factor_sorted ? h->ys_s.as<double>() : h->ys.as<double>();
-    a.zs = h->factor_sorted ? h->zs_s.as<double>() : h->zs.as<double>();
-    a.dsc = h->factor_eq ? h->dsc.as<double>() : nullptr;
-    a.v = h->v;
-    a.exact = h->exact;
-    a.eps = h->eps;
-    a.rl = h->rl;
-    a.nwells = h->nwells;
-    a.nextra = h->nextra;
-    a.wells = h->wells.as<double>();
-    a.extra = h->nextra ? h->extra_rows.as<double>() + t0 : nullptr;
-    a.extra_stride = npt;
-    a.cvec = nf > 0 ? (const double*)h->fc.as<double>() : (const double*)h->cvec.as<double>();
-    a.zout = h->z.as<double>() + t0;
-    // fields 1 .. nf - 1: MIK_FB per launch, read back from the panel the launch of field 0 has just written (same stream, right after it)
-    auto launch_fields = [&](const RhsArgs& a0, bool sp, hipStream_t st) -> int {
-      for (int f0 = 1; f0 < nf; f0 += MIK_FB) {
-        RhsArgs b = a0;
-        b.cvec = h->fc.as<double>() + (size_t)f0 * Mp;
-        b.cf_ld = Mp;
-        b.nfc = std::min(MIK_FB, nf - f0);
-        b.zout = h->zf.as<double>() + (size_t)(f0 - 1) * npt + (sp && b.perm ? 0 : t0);
-        b.zf_ld = npt;
-        if (sp) hipLaunchKernelGGL((k_rhs<0, 0, true, false, MIK_FB>), dim3(palloc / MIK_TP), dim3(256), 0, st, b);
-        else hipLaunchKernelGGL((k_rhs<0, 0, false, false, MIK_FB>), dim3(palloc / MIK_TP), dim3(256), 0, st, b);
-      }
-      HIPC(hipGetLastError());
-      return MIK_OK;
-    };
-    if (two && c >= 2) HIPC(hipStreamWaitEvent(sr, h->pr_events[2 * (c - 2) + 1], 0));  // the contraction that read this panel is done
-    if (sparse) {
-      // candidates (bounding boxes), cleared flags, then delta for the candidate blocks only
-      const SpLane& ln = lane[lanes2 ? (c & 1) : 0];
-      hipStream_t ss = ln.st;
-      a.Bt = ln.Bt->as<double>();
-      a.cand = ln.cand->as<unsigned char>();
-      a.flags = ln.flags->as<unsigned char>();
-      a.nIblk = nIblk;
-      a.nK16 = nK16;
-      a.nKf = nKt;
-      a.sill = h->v.p0 + h->v.p2;
-      if (perm_all) {  // sorted order: the chunk's points are reached through perm, from the list's base pointers
-        a.perm = perm_all + t0;
-        a.px = h->px.as<double>();
-        a.py = h->py.as<double>();
-        a.pz = h->ndim == 3 ? h->pz.as<double>() : nullptr;
-        a.extra = h->nextra ? h->extra_rows.as<double>() : nullptr;
-        a.zout = h->z.as<double>();
-      }
-      HIPC(hipEventRecord(h->evpool[2 + 4 * nchunks + 2 * c], ss));
-      // candidates by bounding boxes: Euclidean coordinates against the range; geographic: unit vectors against the CHORD of the range
-      // (2 sin(arc / 2), the range being degrees of arc; beyond 180 degrees everything is in range)
-      const double *cx = a.px, *cy = a.py, *cz = a.pz;
-      double radius = std::max(h->v.p1, h->eps);
-      if (h->geo) {
-        const long off = perm_all ? 0 : t0;
-        cx = h->gu.as<double>() + off, cy = cx + npt, cz = cy + npt;
-        radius = radius >= 180.0 ? 4.0 : 2.0 * std::sin(radius * 3.14159265358979323846 / 360.0) * (1.0 + 1e-12) + 1e-15;
-      }
-      hipLaunchKernelGGL(k_sp_cand, dim3(palloc / 128), dim3(128), 0, ss, cx, cy, cz, nvalid, (const double*)h->sbox.as<double>(), nK16,
-                         h->N / 16, (h->M + 15) / 16, radius, ln.cand->as<unsigned char>(), a.perm, gathered ? 0 : 1, ln.flags->as<unsigned char>(), nKt);
-      HIPC(hipEventRecord(h->evpool[2 + 4 * c], ss));
-      if (h8) {
-        if (h->geo) hipLaunchKernelGGL((k_rhs<3, 1, true, true>), dim3(palloc / MIK_TP), dim3(256), 0, ss, a);
-        else if (h->ndim == 3) hipLaunchKernelGGL((k_rhs<3, 3, true, true>), dim3(palloc / MIK_TP), dim3(256), 0, ss, a);
-        else hipLaunchKernelGGL((k_rhs<3, 2, true, true>), dim3(palloc / MIK_TP), dim3(256), 0, ss, a);
-      } else if (h->geo) hipLaunchKernelGGL((k_rhs<3, 1, true>), dim3(palloc / MIK_TP), dim3(256), 0, ss, a);
-      else if (h->ndim == 3) hipLaunchKernelGGL((k_rhs<3, 3, true>), dim3(palloc / MIK_TP), dim3(256), 0, ss, a);
-      else hipLaunchKernelGGL((k_rhs<3, 2, true>), dim3(palloc / MIK_TP), dim3(256), 0, ss, a);
-      MIKC(launch_fields(a, true, ss));
-      HIPC(hipEventRecord(h->evpool[3 + 4 * c], ss));
-      return MIK_OK;
-    }
-    HIPC(hipEventRecord(h->evpool[2 + 4 * c], sr));
-    if (h->model == MIK_MODEL_CUSTOM) {
-      DISPATCH_NDIM_FIXED(7, h->geo ? 1 : h->ndim, k_rhs, dim3(palloc / MIK_TP), dim3(256), sr, a);
-      MIKC(custom_roundtrip(h, a.Bt, nvalid, h->N, Mp));
-      DISPATCH_NDIM_FIXED(6, h->geo ? 1 : h->ndim, k_rhs, dim3(palloc / MIK_TP), dim3(256), sr, a);
-    } else {
-      DISPATCH_MODEL_NDIM(h->model, h->geo ? 1 : h->ndim, k_rhs, dim3(palloc / MIK_TP), dim3(256), sr, a);
-    }
-    MIKC(launch_fields(a, false, sr));
-    HIPC(hipEventRecord(h->evpool[3 + 4 * c], sr));
-    if (two) HIPC(hipEventRecord(h->pr_events[2 * c], sr));
-    return MIK_OK;
-  };
-  // a chunk's z of fields 1 .. nf - 1 leave for pin_fz beside its z and sigma^2 (on stream_d2h, behind ev_chunk)
-  auto copy_fields_out = [&](long t0, int nvalid) -> int {
-    for (int f = 1; f < nf; ++f)
-      HIPC(hipMemcpyAsync(h->pin_fz.as<double>() + (size_t)(f - 1) * npt + t0, h->zf.as<double>() + (size_t)(f - 1) * npt + t0,
-                          sizeof(double) * nvalid, hipMemcpyDeviceToHost, h->stream_d2h));
-    return MIK_OK;
-  };
-  if (two) MIKC(launch_rhs(0));
-  for (long c = 0; c < nchunks; ++c) {
-    const long t0 = c * chunk;
-    const int nvalid = (int)std::min<long>(chunk, npt - t0);
-    const int palloc = ((nvalid + 127) / 128) * 128;
-    if (two) {
-      if (c + 1 < nchunks) MIKC(launch_rhs(c + 1));  // queued behind chunk c's right-hand sides on the second stream
-      HIPC(hipStreamWaitEvent(sc, h->pr_events[2 * c], 0));
-    } else {
-      MIKC(launch_rhs(c));
-    }
-    hipEvent_t e1 = h->evpool[4 + 4 * c], e2 = h->evpool[5 + 4 * c];
-    if (sparse) {
-      const int nTb = palloc / 128;
-      const SpLane& ln = lane[lanes2 ? (c & 1) : 0];
-      hipStream_t sc = ln.st;  // (shadows the dense path's stream: this launch lives on its lane's)
-      if (gathered) {
-        hipLaunchKernelGGL(k_sp_lists_g, dim3(nTb), dim3(64), 0, sc, (const unsigned char*)ln.flags->as<unsigned char>(), nKt,
-                           ln.klist->as<unsigned short>(), ln.kcount->as<int>(), ln.nrows->as<int>(), h8 ? 1 : 0);
-        hipLaunchKernelGGL(k_sp_tiles_g<true>, dim3((unsigned)((nTb + h->opt_sparse_group - 1) / h->opt_sparse_group)), dim3(256), 0, sc, (const int*)ln.nrows->as<int>(),
-                           (const int*)ln.kcount->as<int>(), (const unsigned short*)ln.klist->as<unsigned short>(), nKt, nTb, ln.recs->as<uint4>(),
-                           ln.xoff->as<int>(), h->sp_stats.as<unsigned long long>() + 4 * c, h->opt_sparse_group, ln.queue->as<unsigned long long>());
-      } else {
-        hipLaunchKernelGGL(k_sp_lists, dim3(nTb), dim3(64), 0, sc, (const unsigned char*)ln.flags->as<unsigned char>(), nK16, nIblk,
-                           ln.klist->as<unsigned short>(), ln.kcount->as<int>(), ln.rows->as<unsigned short>(),
-                           ln.rstart->as<unsigned short>(), ln.nrows->as<int>());
-        hipLaunchKernelGGL(k_sp_tiles, dim3(1), dim3(1024), 0, sc, (const int*)ln.nrows->as<int>(), (const int*)ln.kcount->as<int>(),
-                           (const unsigned short*)ln.rstart->as<unsigned short>(), nIblk, nTb, ln.tiles->as<unsigned>(),
-                           ln.xoff->as<int>(), h->sp_stats.as<unsigned long long>() + 4 * c);
-      }
-      HIPC(hipEventRecord(h->evpool[3 + 4 * nchunks + 2 * c], sc));
-      if (!gathered) HIPC(hipMemsetAsync(ln.queue->p, 0, 8 * sizeof(unsigned long long), sc));  // (gathered: k_sp_tiles_g zeroes the queues)
-      SpArgs sa{};
-      sa.Ainv = h->T.as<double>();
-      sa.lda = Mp;
-      sa.Bt = ln.Bt->as<double>();
-      sa.ldb = Mp;
-      sa.part = ln.part->as<double>();
-      sa.palloc = palloc;
-      sa.kend = kend;
-      sa.nIblk = nIblk;
-      sa.nK16 = nK16;
-      sa.klist = ln.klist->as<unsigned short>();
-      sa.kcount = ln.kcount->as<int>();
-      sa.rows = ln.rows->as<unsigned short>();
-      sa.rstart = ln.rstart->as<unsigned short>();
-      sa.tiles = ln.tiles->as<unsigned>();
-      sa.xoff = ln.xoff->as<int>();
-      sa.queue = ln.queue->as<unsigned long long>();
-      // two lanes: the CONTRACTIONS run one after the other (this one behind the other lane's previous one); what overlaps a contraction is the
-      // other lane's candidate / right-hand-side / list kernels in its tail.  Two persistent launches side by side share every CU and mix two
-      // tile queues in every XCD's L2: measured 3.5 % slower per pair (profiles/r06_predict_timeline_c5.txt; rounds 4-5 got this order by accident:
-      // the queue memset in front of the contraction waited for a free CU).
-      if (lanes2 && c > 0) HIPC(hipStreamWaitEvent(sc, h->evpool[5 + 4 * (c - 1)], 0));
-      HIPC(hipEventRecord(e1, sc));
-      if (gathered) {
-        SpgArgs ga{};
-        ga.Ainv = sa.Ainv;
-        ga.lda = Mp;
-        ga.Bt = sa.Bt;
-        ga.ldb = Mp;
-        ga.part = sa.part;
-        ga.palloc = palloc;
-        ga.nK16 = nKt;
-        ga.klist = sa.klist;
-        ga.recs = ln.recs->as<uint4>();
-        ga.xoff = sa.xoff;
-        ga.queue = sa.queue;
-        static const bool spg_prof = getenv("MIK_SPG_PROF") && atoi(getenv("MIK_SPG_PROF")) != 0;
-        if (spg_prof) {  // diagnostic (MIK_SPG_PROF=1): cycle sums per phase of the tile loop, one launch, printed to stderr
-          const unsigned nb = (unsigned)std::min<long>(2L * h->n_cu, (long)nTb * nIblk);
-          static DevBuf pb;
-          MIKC(pb.ensure(sizeof(unsigned long long) * nb * 96));
-          HIPC(hipMemsetAsync(pb.p, 0, pb.bytes, sc));
-          ga.prof = pb.as<unsigned long long>();
-          hipLaunchKernelGGL((k_contract_spg<2, true, true, true>), dim3(nb), dim3(512), 0, sc, ga);
-          std::vector<unsigned long long> hp((size_t)nb * 96);
-          HIPC(hipMemcpyAsync(hp.data(), pb.p, sizeof(unsigned long long) * hp.size(), hipMemcpyDeviceToHost, sc));
-          HIPC(hipStreamSynchronize(sc));
-          static const char* names[8] = {"top drain+barrier", "off-diagonal K steps", "triangle K steps", "acquire", "adopt", "epilogue loads+sums", "reduce+store", "-"};
-          {
-            double c[16] = {0};
-            for (unsigned b = 0; b < nb; ++b)
-              for (int i = 0; i < 16; ++i) c[i] += (double)hp[(size_t)nb * 80 + (size_t)b * 16 + i];
-            fprintf(stderr, "spg triangle steps (cycles per visit):");
-            for (int w = 7; w >= 0; --w) fprintf(stderr, "  w=%d %.0f", w, c[w] / std::max(1.0, c[8 + w]));
-            fprintf(stderr, "\n");
-          }
-          for (int wv : {0, 6}) {
-            double sum[10] = {0};
-            for (unsigned b = 0; b < nb; ++b)
-              for (int i = 0; i < 10; ++i) sum[i] += (double)hp[((size_t)b * 8 + wv) * 10 + i];
-            double tot = 0;
-            for (int i = 0; i < 7; ++i) tot += sum[i];
-            fprintf(stderr, "spg phases, wavefront %d: %.0f tiles of the launch, %.1f per block, %.1f off-diagonal steps per tile, %.0f cycles per tile\n", wv, sum[8], sum[8] / nb, sum[9] / std::max(1.0, sum[8]), tot / std::max(1.0, sum[8]));
-            for (int i = 0; i < 7; ++i) fprintf(stderr, "   %-22s %8.0f cycles per tile  %5.1f %%\n", names[i], sum[i] / std::max(1.0, sum[8]), 100.0 * sum[i] / tot);
-            fprintf(stderr, "   per off-diagonal step %.0f cycles\n", sum[1] / std::max(1.0, sum[9]));
-          }
-        } else
-        // (2 n_cu persistent blocks: leaving 32 .. 128 of the slots to the other lane's preparation kernels was tried -- they then run beside the
-        // contraction at a fraction of the chip -- and measured a tie at 32 and 1 - 3 % slower beyond: profiles/r06_predict_timeline_c5_after.txt)
-        hipLaunchKernelGGL((k_contract_spg<2, true, true>), dim3((unsigned)std::min<long>(2L * h->n_cu, (long)nTb * nIblk)), dim3(512), 0, sc, ga);
-      } else {
-        hipLaunchKernelGGL((k_contract_sp<2>), dim3((unsigned)std::min<long>(2L * h->n_cu, (long)nTb * nIblk)), dim3(512), 0, sc, sa);
-      }
-      HIPC(hipEventRecord(e2, sc));
-      hipLaunchKernelGGL(k_ss_reduce_sp, dim3((nvalid + 255) / 256), dim3(256), 0, sc, (const double*)ln.part->as<double>(), palloc,
-                         (const int*)ln.nrows->as<int>(), nvalid, 2.0 * (h->v.p0 + h->v.p2),
-                         perm_all ? h->ss.as<double>() : h->ss.as<double>() + t0, perm_all ? perm_all + t0 : (const unsigned*)nullptr);
-      if (lanes2 && (c & 1)) HIPC(hipEventRecord(h->pr_events[0], sc));  // lane 1's latest launch (joined below)
-      HIPC(hipEventRecord(h->ev_chunk, sc));
-      HIPC(hipStreamWaitEvent(h->stream_d2h, h->ev_chunk, 0));
-      HIPC(hipMemcpyAsync(h->pin_out.as<double>() + t0, h->z.as<double>() + t0, sizeof(double) * nvalid, hipMemcpyDeviceToHost,
-                          h->stream_d2h));
-      HIPC(hipMemcpyAsync(h->pin_out.as<double>() + npt + t0, h->ss.as<double>() + t0, sizeof(double) * nvalid,
-                          hipMemcpyDeviceToHost, h->stream_d2h));
-      MIKC(copy_fields_out(t0, nvalid));
-      h->tm.sparse_tiles_dense += (double)nTb * nIblk;
-      h->tm.sparse_ktiles_dense += (double)nTb * (kend / 16.0) * (nIblk - 1) / 2.0;  // off-diagonal K tiles of the dense symmetric form (about)
-      continue;
-    }
-    HIPC(hipEventRecord(e1, sc));
-    const long tiles = (long)nIblk * (palloc / 128);
-    const unsigned grid = (unsigned)(8 * ((tiles + 7) / 8));
-    {
-      const double* Ai = h->T.as<double>();
-      const double* Bi = (two && (c & 1)) ? h->Bt2.as<double>() : h->Bt.as<double>();
-      double* pp = h->part.as<double>();
-      const long ldm = Mp;
-      const unsigned sgrid = (unsigned)super_grid(nIblk, palloc / 128);
-      // persistent launch: 2 blocks per CU pop tiles from per-XCD sequences (8 counters, zeroed per launch); 8 wavefronts per tile
-      // (wave tile 32 x 64).  Three forms: the symmetric half product with triangular diagonal blocks (default), with whole
-      // diagonal blocks ("tri" 0) and the reference's full product w = A_inv b ("symmetric" 0) -- the cross-checks of the parity tests.
-      // (The 4-wave tiles, the v_fma_f64 engine, pair units, popped-ahead tiles: every A/B of rounds 2-5 lost; tools/kernel_bench.)
-      MIKC(h->queue.ensure(8 * sizeof(unsigned long long)));
-      HIPC(hipMemsetAsync(h->queue.p, 0, 8 * sizeof(unsigned long long), sc));
-      unsigned long long* qp = h->queue.as<unsigned long long>();
-      const unsigned pgrid = (unsigned)std::min<long>(2L * h->n_cu, (long)sgrid);
-      if (h->opt_sym && h->opt_tri) hipLaunchKernelGGL((k_contract<true, 2, true, false, true>), dim3(pgrid), dim3(512), 0, sc, Ai, ldm, Bi, ldm, pp, palloc, nIblk, kend, qp);
-      else if (h->opt_sym) hipLaunchKernelGGL((k_contract<true, 2>), dim3(pgrid), dim3(512), 0, sc, Ai, ldm, Bi, ldm, pp, palloc, nIblk, kend, qp);
-      else hipLaunchKernelGGL((k_contract<false, 2>), dim3(pgrid), dim3(512), 0, sc, Ai, ldm, Bi, ldm, pp, palloc, nIblk, kend, qp);
-    }
-    HIPC(hipEventRecord(e2, sc));
-    if (two) HIPC(hipEventRecord(h->pr_events[2 * c + 1], sc));
-    hipLaunchKernelGGL(k_ss_reduce, dim3((nvalid + 255) / 256), dim3(256), 0, sc, (const double*)h->part.as<double>(),
-                       palloc, nIblk, nvalid, h->ss.as<double>() + t0);
-    // this chunk's z and sigma^2 leave for the page-locked landing zone while the next chunk is computed
-    HIPC(hipEventRecord(h->ev_chunk, sc));
-    HIPC(hipStreamWaitEvent(h->stream_d2h, h->ev_chunk, 0));
-    HIPC(hipMemcpyAsync(h->pin_out.as<double>() + t0, h->z.as<double>() + t0, sizeof(double) * nvalid, hipMemcpyDeviceToHost,
-                        h->stream_d2h));
-    HIPC(hipMemcpyAsync(h->pin_out.as<double>() + npt + t0, h->ss.as<double>() + t0, sizeof(double) * nvalid,
-                        hipMemcpyDeviceToHost, h->stream_d2h));
-    MIKC(copy_fields_out(t0, nvalid));
-    // executed flops of this launch: per tile 2*128*128*(k extent)
-    // (triangular diagonal blocks: nt (nt + 1) / 2 products of 16 rows x 16 k instead of 8 nt, nt = K tiles of the block)
-    const bool tri = h->opt_sym && h->opt_tri;
-    double kext = 0.0;
-    for (int ib = 0; ib < nIblk; ++ib) {
-      const int ext = h->opt_sym ? std::max(0, kend - ib * 128) : kend;
-      if (tri) {
-        const int nt = std::min(ext, 128) / 16;
-        kext += (ext - 16 * nt) + 16.0 * (nt * (nt + 1) / 2) / 8.0;
-      } else kext += ext;
-    }
-    h->tm.contract_flops_executed += 2.0 * 128.0 * 128.0 * kext * (palloc / 128);
+  if (p.sortpts) p.perm = h->ps_idx[0].as<unsigned>();
+  if (p.lanes2) HIPC(hipStreamWaitEvent(h->stream2, h->ev_predict0, 0));
+  if (p.lanes2 && sorted_now) HIPC(hipStreamWaitEvent(h->stream2, h->ev_sort, 0));
+  for (long c = 0; c < p.nchunks; ++c) {
+    const Launch l(p, c);
+    const int L = p.lanes2 ? (int)(c & 1) : 0;  // lane 0 on the handle's stream, lane 1 on stream2
+    hipStream_t st = L ? h->stream2 : h->stream;
+    MIKC(launch_rhs(h, p, l, h->lane[L], st));
+    MIKC(p.sparse ? contract_sparse(h, p, l, h->lane[L], st) : contract_dense(h, p, l));
+    MIKC(copy_out(h, p, l, st));
   }
   HIPC(hipGetLastError());
-  if (lanes2) HIPC(hipStreamWaitEvent(h->stream, h->pr_events[0], 0));  // the handle's stream ends behind both lanes
-  HIPC(hipEventRecord(h->evpool[1], h->stream));
+  if (p.lanes2) HIPC(hipStreamWaitEvent(h->stream, h->ev_lane1, 0));  // the handle's stream ends behind both lanes
+  HIPC(hipEventRecord(h->ev_predict1, h->stream));
   HIPC(hipEventRecord(h->ev_d2h, h->stream_d2h));
   HIPC(hipStreamSynchronize(h->stream));
-  float ms = 0.f;
-  HIPC(hipEventElapsedTime(&ms, h->evpool[0], h->evpool[1]));
-  h->tm.predict_ms = ms;
-  if (sorted_now) {
-    HIPC(hipEventElapsedTime(&ms, h->evpool[0], h->ev_sort));
-    h->tm.sort_points_ms = ms;
-  }
-  for (long c = 0; c < nchunks; ++c) {
-    HIPC(hipEventElapsedTime(&ms, h->evpool[2 + 4 * c], h->evpool[3 + 4 * c]));
-    h->tm.rhs_ms += ms;
-    HIPC(hipEventElapsedTime(&ms, h->evpool[4 + 4 * c], h->evpool[5 + 4 * c]));
-    h->tm.contract_ms += ms;
-  }
-  if (sparse) {
-    HIPC(hipMemcpy(sp_host.data(), h->sp_stats.p, sizeof(unsigned long long) * sp_host.size(), hipMemcpyDeviceToHost));
-    const int ntl = (kend - (nIblk - 1) * 128) / 16;  // K tiles of the (short) last block
-    for (long c = 0; c < nchunks; ++c) {
-      HIPC(hipEventElapsedTime(&ms, h->evpool[2 + 4 * nchunks + 2 * c], h->evpool[2 + 4 * c]));
-      h->tm.sparse_lists_ms += ms;
-      HIPC(hipEventElapsedTime(&ms, h->evpool[3 + 4 * c], h->evpool[3 + 4 * nchunks + 2 * c]));
-      h->tm.sparse_lists_ms += ms;
-      const long nTb = (std::min<long>(chunk, npt - c * chunk) + 127) / 128;
-      const double tiles = (double)sp_host[4 * c], offk = (double)sp_host[4 * c + 1];
-      h->tm.sparse_tiles += tiles;
-      h->tm.sparse_ktiles += offk;
-      // executed flops: off-diagonal K tiles are 128 x 16 x 128 products; a diagonal block is nt (nt + 1) / 2 products of 16 rows x 16 k
-      // x 128 points (nt = 8, or the short last block's -- every point block has that row block: the last row is the 1 of ok.py:673;
-      // gathered groups: k_sp_tiles_g counted the products of the triangular parts, short last tiles included)
-      const double diagp = gathered ? (double)sp_host[4 * c + 2] : 36.0 * std::max(0.0, tiles - (double)nTb) + (ntl * (ntl + 1) / 2) * (double)nTb;
-      h->tm.sparse_diag_products += diagp;
-      h->tm.contract_flops_executed += 2.0 * 128.0 * 16.0 * 128.0 * offk + 2.0 * 16.0 * 16.0 * 128.0 * diagp;
-    }
-  }
-  h->tm.contract_launches = nchunks;
-  h->tm.rhs_overlapped = two ? 1 : 0;
+  MIKC(read_back(h, p, sorted_now));
   h->have_results = true;
   return MIK_OK;
 }

@@ -38,6 +38,9 @@ static int create_one_body(mik_handle* h, int device) {
   HIPC(hipEventCreateWithFlags(&h->ev_d2h, hipEventDisableTiming));
   HIPC(hipEventCreateWithFlags(&h->ev_chunk, hipEventDisableTiming));
   HIPC(hipEventCreate(&h->ev_sort));
+  HIPC(hipEventCreate(&h->ev_predict0));
+  HIPC(hipEventCreate(&h->ev_predict1));
+  HIPC(hipEventCreateWithFlags(&h->ev_lane1, hipEventDisableTiming));
   {
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) h->n_cu = ncu;
@@ -54,8 +57,6 @@ static int create_one_body(mik_handle* h, int device) {
   if (env && atoi(env) >= -1 && atoi(env) <= 2) h->opt_sparse = atoi(env);
   env = getenv("MIK_SORT_POINTS");
   if (env && atoi(env) >= -1 && atoi(env) <= 1) h->opt_sort_points = atoi(env);
-  env = getenv("MIK_SPARSE_GROUP");
-  if (env && atoi(env) >= 1 && atoi(env) <= 16) h->opt_sparse_group = atoi(env);
   env = getenv("MIK_SPARSE_ROWS");
   if (env && (atoi(env) == -1 || atoi(env) == 16 || atoi(env) == 128)) h->opt_sparse_rows = atoi(env);
   env = getenv("MIK_UPDATE_REV");
@@ -70,8 +71,6 @@ static int create_one_body(mik_handle* h, int device) {
   if (env) h->opt_exchange_tri = atoi(env) ? 1 : 0;
   env = getenv("MIK_ALIAS_DEVICES");
   if (env) h->alias_ok = atoi(env) != 0;
-  env = getenv("MIK_RHS_OVERLAP");
-  if (env) h->opt_rhs_overlap = atoi(env) ? 1 : 0;
   env = getenv("MIK_ASYNC_EXCHANGE");
   if (env && atoi(env) >= 0 && atoi(env) <= 2) h->opt_async_exchange = atoi(env);
   h->rccl_init_limit = env_seconds("MIK_RCCL_INIT_TIMEOUT", 120.0);
@@ -112,20 +111,22 @@ static void destroy_one(mik_handle* h) {
                     &h->Rt, &h->TKt, &h->Dinv, &h->DinvT, &h->P0, &h->P1, &h->cand0, &h->cand1, &h->pivall, &h->flag,
                     &h->Cold2, &h->Cnew2, &h->Rt2, &h->Dinv2, &h->DinvT2, &h->Dinv3, &h->DinvT3, &h->Dnext, &h->Dcopy, &h->Rb, &h->grid.gx, &h->grid.gy, &h->grid.gz, &h->grid.orig,
                     &h->grid.cstart,
-                    &h->px, &h->py, &h->pz, &h->grid_axes, &h->grid_idx, &h->Averify, &h->vbuf, &h->extra_rows, &h->z, &h->ss, &h->Bt, &h->Bt2, &h->part, &h->mw_idx, &h->mw_dist, &h->stat_S, &h->stat_x, &h->stat_out, &h->queue,
-                    &h->xs_s, &h->ys_s, &h->zs_s, &h->vals_s, &h->extra_cols_s, &h->sbox, &h->sp_cand, &h->sp_flags, &h->sp_klist, &h->sp_kcount,
-                    &h->sp_nrows, &h->sp_rows, &h->sp_rstart, &h->sp_tiles, &h->sp_xoff, &h->sp_stats, &h->sp2_cand, &h->sp2_flags, &h->sp2_klist, &h->sp2_kcount,
-                    &h->sp2_nrows, &h->sp2_rows, &h->sp2_rstart, &h->sp2_tiles, &h->sp2_xoff, &h->part2, &h->queue2, &h->dsc, &h->sp_recs, &h->sp2_recs, &h->ps_key[0], &h->ps_key[1], &h->ps_idx[0], &h->ps_idx[1], &h->ps_table, &h->ps_box, &h->ps_x, &h->ps_y, &h->ps_z, &h->ps_zs, &h->ps_sss, &h->xpack, &h->fv, &h->fc, &h->zf};
+                    &h->px, &h->py, &h->pz, &h->grid_axes, &h->grid_idx, &h->Averify, &h->vbuf, &h->extra_rows, &h->z, &h->ss, &h->mw_idx, &h->mw_dist, &h->stat_S, &h->stat_x, &h->stat_out,
+                    &h->xs_s, &h->ys_s, &h->zs_s, &h->vals_s, &h->extra_cols_s, &h->sbox, &h->sp_stats, &h->dsc, &h->ps_key[0], &h->ps_key[1], &h->ps_idx[0], &h->ps_idx[1], &h->ps_table, &h->ps_box, &h->ps_x, &h->ps_y, &h->ps_z, &h->ps_zs, &h->ps_sss, &h->xpack, &h->fv, &h->fc, &h->zf};
   for (DevBuf* b : bufs) b->release();
+  for (PredictLane& L : h->lane)
+    for (DevBuf* b : {&L.cand, &L.flags, &L.klist, &L.kcount, &L.nrows, &L.rows, &L.rstart, &L.tiles, &L.xoff, &L.recs, &L.part, &L.queue, &L.Bt}) b->release();
   h->pin_in.release();
   h->pin_out.release();
   h->pin_fz.release();
   for (hipEvent_t e : h->evpool) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->la_events) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ps_events) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h->pr_events) (void)hipEventDestroy(e);
-  if (h->ev_chunk) (void)hipEventDestroy(h->ev_chunk);
-  if (h->ev_sort) (void)hipEventDestroy(h->ev_sort);
+  for (LaunchEvents& ev : h->pr_launch)
+    for (hipEvent_t* e : ev.all())
+      if (*e) (void)hipEventDestroy(*e);
+  for (hipEvent_t e : {h->ev_chunk, h->ev_sort, h->ev_predict0, h->ev_predict1, h->ev_lane1})
+    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->xevents) (void)hipEventDestroy(e);
   if (h->ev_d2h) (void)hipEventDestroy(h->ev_d2h);
   if (h->stream_d2h) (void)hipStreamDestroy(h->stream_d2h);
@@ -184,9 +185,9 @@ static int set_group(mik_handle* h, int n) {
     }
     k->is_kid = true;
     k->opt_factor = h->opt_factor, k->opt_sym = h->opt_sym;
-    k->opt_chunk = h->opt_chunk, k->opt_symsweep = h->opt_symsweep, k->opt_panel_stream = h->opt_panel_stream, k->opt_update_rev = h->opt_update_rev, k->opt_lookahead = h->opt_lookahead, k->opt_gate = h->opt_gate, k->opt_pinv_fast = h->opt_pinv_fast, k->opt_rhs_overlap = h->opt_rhs_overlap, k->opt_verify = h->opt_verify, k->verify_tol_z = h->verify_tol_z, k->verify_tol_inv = h->verify_tol_inv;
+    k->opt_chunk = h->opt_chunk, k->opt_symsweep = h->opt_symsweep, k->opt_panel_stream = h->opt_panel_stream, k->opt_update_rev = h->opt_update_rev, k->opt_lookahead = h->opt_lookahead, k->opt_gate = h->opt_gate, k->opt_pinv_fast = h->opt_pinv_fast, k->opt_verify = h->opt_verify, k->verify_tol_z = h->verify_tol_z, k->verify_tol_inv = h->verify_tol_inv;
     k->opt_mw_class = h->opt_mw_class, k->opt_mw_knn_bound = h->opt_mw_knn_bound, k->opt_mw_pivot = h->opt_mw_pivot, k->opt_mw_lds_cap = h->opt_mw_lds_cap, k->opt_tri = h->opt_tri, k->opt_symmetrize = h->opt_symmetrize;
-    k->opt_sparse = h->opt_sparse, k->opt_sparse_lanes = h->opt_sparse_lanes, k->opt_sparse_rows = h->opt_sparse_rows, k->opt_sparse_group = h->opt_sparse_group, k->opt_sort_points = h->opt_sort_points, k->opt_drift_eq = h->opt_drift_eq;
+    k->opt_sparse = h->opt_sparse, k->opt_sparse_lanes = h->opt_sparse_lanes, k->opt_sparse_rows = h->opt_sparse_rows, k->opt_sort_points = h->opt_sort_points, k->opt_drift_eq = h->opt_drift_eq;
     k->opt_pinv_block = h->opt_pinv_block, k->opt_mw_static = h->opt_mw_static, k->opt_mw_knn_lane = h->opt_mw_knn_lane;
     k->custom_fn = h->custom_fn, k->custom_user = h->custom_user;
     h->kids.push_back(k);
@@ -273,9 +274,6 @@ int mik_set_option(mik_handle* h, const char* key, double value) {
   } else if (!strcmp(key, "sort_points")) {
     if (value != -1.0 && value != 0.0 && value != 1.0) return fail(MIK_EINVAL, "sort_points must be -1 (auto), 0 or 1");
     h->opt_sort_points = (int)value;
-  } else if (!strcmp(key, "sparse_group")) {
-    if (!(value >= 1.0 && value <= 16.0)) return fail(MIK_EINVAL, "sparse_group must be 1 .. 16");
-    h->opt_sparse_group = (int)value;
   } else if (!strcmp(key, "sparse_rows")) {
     if (value != -1.0 && value != 16.0 && value != 128.0) return fail(MIK_EINVAL, "sparse_rows must be -1 (auto), 16 or 128");
     h->opt_sparse_rows = (int)value;
@@ -293,8 +291,6 @@ int mik_set_option(mik_handle* h, const char* key, double value) {
     h->opt_chunk = ((long)value / 128) * 128;
   } else if (!strcmp(key, "symsweep")) {
     h->opt_symsweep = value < 0.0 ? -1 : (value != 0.0);
-  } else if (!strcmp(key, "rhs_overlap")) {
-    h->opt_rhs_overlap = value != 0.0;
   } else if (!strcmp(key, "verify")) {
     h->opt_verify = value != 0.0;
   } else if (!strcmp(key, "verify_tol_z") || !strcmp(key, "verify_tol_inv")) {

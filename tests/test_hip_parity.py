@@ -259,7 +259,7 @@ def test_options_that_left_the_library_are_refused():
     lib = _lib()
     h = lib.Handle(0)
     for key in ("update_deep", "update_tpb", "pivot256", "update_pf", "update_token", "wide_reserve", "wide_colstream", "engine", "waves", "update_waves",
-                "panel_rows", "update_map", "diag", "early_diag", "fuse_chain", "sparse_ktile", "sparse_epilogue"):
+                "panel_rows", "update_map", "diag", "early_diag", "fuse_chain", "sparse_ktile", "sparse_epilogue", "rhs_overlap", "sparse_group"):
         with pytest.raises(ValueError, match="unknown option"):
             h.set_option(key, 1)
     h.close()
