@@ -36,10 +36,11 @@ extern "C" {
  *   4 -> 5  mik_grid.cell_count == 0 is an EMPTY range (it used to mean "the whole grid", which is now -1): a caller that
  *           zero-initialises mik_grid must set cell_count = -1.  mik_abi_version() returns the library's value; the Python
  *           loader (pykrige_amd/_lib.py) refuses a library whose version differs from the header it was written against. */
-#define MIK_ABI_VERSION 7
+#define MIK_ABI_VERSION 8
 /*   5 -> 6  mik_timing grew by sparse_ktile + reserved2 (8 bytes appended; earlier fields unchanged). */
 /*   6 -> 7  mik_timing grew by exchange_bytes (8 bytes appended); the factor exchange moves the packed upper block triangle of the inverse
  *           (option "exchange_tri"); the option keys of the experiments of rounds 2-5 are refused (see the option list). */
+/*   7 -> 8  mik_predict_moving_window kriges the value fields of mik_set_fields (it returned MIK_EINVAL with fields set). */
 
 #define MIK_OK          0
 #define MIK_EINVAL     (-1) /* bad argument            -> Python ValueError                  */
@@ -352,7 +353,13 @@ void mik_release_results(double *z);                       /* gives such a buffe
  * twice, sigma^2 is computed once.  z of field f is bit for bit the z of a mik_predict whose factor was formed with field f as
  * the problem's values -- the variogram and the drift set-up are the problem's, and so is the factor path the probe of the
  * inverse chose (it tests the problem's own values).  The planes of fields 1 .. nf - 1 go to a page-locked landing zone chunk by chunk,
- * as z does.  Not with mik_predict_moving_window (MIK_EINVAL). */
+ * as z does.
+ * mik_predict_moving_window kriges every field as well (ABI 8): the neighbour search and the local right-hand sides run once, the fields
+ * enter only the per-point solvers -- the LDL^T kernel (windows up to 256) eliminates up to G - 2 of them per pass as further
+ * right-hand-side rows (G = 4, 8, 16, 32: the thread grid of the window's class), the pivoting and blocked solvers take one per launch.
+ * z of field f is bit for bit the z of a moving-window predict whose problem values are field f, sigma^2 is computed as without fields;
+ * mik_get_results / mik_take_results return field 0 and sigma^2, mik_get_field_results the nf planes.  The device planes are bounded
+ * to ~2 GB by groups of fields (a further group repeats the search). */
 int  mik_set_fields(mik_handle *h, const double *values, int64_t n, int32_t nf);
 int  mik_get_field_results(mik_handle *h, double *z_out);  /* nf x npt doubles, plane f = field f, each scattered through the mask like
                                                               mik_get_results (masked points 0.0 in every plane); call it before
@@ -362,7 +369,8 @@ int  mik_synchronize(mik_handle *h);                       /* wait until the han
 
 /* Moving-window ordinary kriging (n_closest_points): replaces cKDTree.query + _c_exec_loop_moving_window
  * (ok.py:929-986, lib/cok.pyx:98-193; ok3d.py:901-912, 697-733).  Needs mik_set_problem + mik_set_points
- * (no mik_factor: each point solves its own (k+1)x(k+1) system).  Results as for mik_predict. */
+ * (no mik_factor: each point solves its own (k+1)x(k+1) system).  Results as for mik_predict; with value fields set
+ * (mik_set_fields) every field is kriged, see there. */
 int  mik_predict_moving_window(mik_handle *h, int n_closest_points);
 
 /* Variogram-fit statistics: replaces core._find_statistics -> core._krige (core.py:759-836, 654-756): for

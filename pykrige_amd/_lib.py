@@ -69,7 +69,7 @@ class MikTiming(C.Structure):
 
 
 _lib = None
-ABI_VERSION = 7  # include/mikrige.h MIK_ABI_VERSION
+ABI_VERSION = 8  # include/mikrige.h MIK_ABI_VERSION
 
 # every entry point include/mikrige.h declares: name -> (restype, argtypes)
 SIGNATURES = {

@@ -497,6 +497,7 @@ int ensure_factor_buffers(mik_handle* h);                                       
 int launch_mirror_upper(double* T, long Mp, hipStream_t st);                                                         // mik_inverse.hip
 int one_factor(mik_handle* h);                                                                                   // mik_inverse.hip
 int sort_points(mik_handle* h, long chunk, long nchunks);                                                        // mik_predict.hip
+int upload_fields(mik_handle* h, int want);                                                                      // mik_predict.hip
 int one_predict(mik_handle* h);                                                                                  // mik_predict.hip
 int one_predict_mw(mik_handle* h, int n_closest);
 // mik_mw_chol.hip, part N: launches class 100 G + RI of k_mw_chol if it holds it, else returns MIK_MWC_NOCLASS

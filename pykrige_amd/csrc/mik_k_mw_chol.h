@@ -20,6 +20,10 @@ struct MwArgs {
   double* z;
   double* ss;
   int* flag;
+  // value rows per point (k_mw_chol only; the other solvers read Z and write z once): 1 = Z -> z; several value fields (mik_set_fields):
+  // row r reads Z + r zstride and writes z + r pstride, r < nrow <= G - 2 of the class
+  int nrow;
+  long zstride, pstride;
 };
 
 // variogram selected at run time (a wave-uniform switch; the moving-window kernels are not instantiated per model)
@@ -95,17 +99,17 @@ __device__ __forceinline__ double mw_entry_t(const Vario& v, int mode, double x1
 template <int G, int RI, int MODEL = -1>
 __global__ void __launch_bounds__((G * G < 256) ? 256 : G * G, MIK_MWC_WAVES(G, RI)) k_mw_chol(MwArgs a) {
   extern __shared__ double mw_lds[];
-  constexpr int T = G * G, NT = T < 256 ? 256 : T, NB = G * RI, ACOL = NB + 4;
-  const int K = a.K;
+  constexpr int T = G * G, NT = T < 256 ? 256 : T, NB = G * RI;
+  const int K = a.K, NR = 2 + a.nrow;  // right-hand-side rows: b + s, 1, then the a.nrow value rows
+  const int ACOL = NB + 1 + NR, PER = 2 * ACOL + (4 + a.nrow) * NB + (1 + NR) * NB;  // one value row: NB + 4 and 2 ACOL + 9 NB
   const int g = threadIdx.x / T, lt = threadIdx.x % T, ty = lt / G, tx = lt % G;
-  constexpr int PER = 2 * ACOL + 9 * NB;
-  double* acol = mw_lds + (long)g * PER;  // [2][ACOL]: column c of the trailing matrix by global row, right-hand-side rows at NB..NB+2
+  double* acol = mw_lds + (long)g * PER;  // [2][ACOL]: column c of the trailing matrix by global row, 1 / d(c) at NB, right-hand-side rows from NB + 1
   double* csx = acol + 2 * ACOL;
   double* csy = csx + NB;
   double* csz = csy + NB;
   double* bvec = csz + NB;
-  double* zsel = bvec + NB;
-  double* ylog = zsel + NB;  // [4][NB]: per step c the three eliminated right-hand-side entries y_q(c) and 1 / d(c)
+  double* zsel = bvec + NB;            // [nrow][NB]
+  double* ylog = zsel + a.nrow * NB;   // [1 + NR][NB]: per step c 1 / d(c), then the eliminated right-hand-side entries y_q(c)
   const long pt = (long)blockIdx.x * (NT / T) + g;
   const bool live = pt < a.npt;
   auto sync = [&]() {
@@ -118,9 +122,10 @@ __global__ void __launch_bounds__((G * G < 256) ? 256 : G * G, MIK_MWC_WAVES(G, 
     }
   };
   for (int r = lt; r < NB; r += T) {
-    double x = 0.0, y = 0.0, z = 0.0, b = 0.0, zv = 0.0;
+    double x = 0.0, y = 0.0, z = 0.0, b = 0.0;
+    int st = -1;
     if (live && r < K) {
-      const int st = a.idx[pt * K + r];
+      st = a.idx[pt * K + r];
       x = a.sx[st];
       y = a.sy[st];
       z = (a.mode == 3) ? a.sz[st] : 0.0;
@@ -130,9 +135,9 @@ __global__ void __launch_bounds__((G * G < 256) ? 256 : G * G, MIK_MWC_WAVES(G, 
         z = sin(lat);
       }
       b = a.dist[pt * K + r];  // dist holds b = -gamma(d), 0 on an exact hit (k_mw_rhs)
-      zv = a.Z[st];
     }
-    csx[r] = x, csy[r] = y, csz[r] = z, bvec[r] = b, zsel[r] = zv;
+    csx[r] = x, csy[r] = y, csz[r] = z, bvec[r] = b;
+    for (int q = 0; q < a.nrow; ++q) zsel[q * NB + r] = st >= 0 ? a.Z[st + q * a.zstride] : 0.0;
   }
   sync();
   double shift;
@@ -165,7 +170,7 @@ __global__ void __launch_bounds__((G * G < 256) ? 256 : G * G, MIK_MWC_WAVES(G, 
   for (int j = 0; j < RI; ++j) {
     const int col = tx + G * j;
     double v = 0.0;
-    if (col < K) v = (ty == 0) ? bvec[col] + shift : (ty == 1) ? 1.0 : (ty == 2) ? zsel[col] : 0.0;
+    if (col < K) v = (ty == 0) ? bvec[col] + shift : (ty == 1) ? 1.0 : (ty < NR) ? zsel[(ty - 2) * NB + col] : 0.0;
     rhs[j] = v;
   }
   int bad = 0;
@@ -180,13 +185,13 @@ __global__ void __launch_bounds__((G * G < 256) ? 256 : G * G, MIK_MWC_WAVES(G, 
         // nor the column factors read back need a select of their own (round 6: one select at the G publishers instead of two in every thread)
 #pragma unroll
         for (int i = cc; i < RI; ++i) ab[ty + G * i] = (i == cc && ty <= cx) ? 0.0 : m[i][cc];
-        if (ty < 3) ab[NB + ty] = rhs[cc];
+        if (ty < NR) ab[NB + 1 + ty] = rhs[cc];
         // the pivot's owner (thread (cx, cx), local tile element (cc, cc)) publishes its reciprocal as well: one wavefront
         // per step pays for it instead of every one (this kernel is instruction-issue bound: round 3)
-        if (ty == cx) ab[NB + 3] = pivot_recip(m[cc][cc]);
+        if (ty == cx) ab[NB] = pivot_recip(m[cc][cc]);
       }
       sync();
-      const double inv = ab[NB + 3];
+      const double inv = ab[NB];
       if (!(inv > 0.0) || !(inv < 1e300)) bad = 2;  // a non-positive (or vanished) pivot
       double u[RI], w[RI];
 #pragma unroll
@@ -194,10 +199,10 @@ __global__ void __launch_bounds__((G * G < 256) ? 256 : G * G, MIK_MWC_WAVES(G, 
         if (!MIK_MWC_LEAN(G, RI)) u[i] = ab[ty + G * i] * inv;
         w[i] = ab[tx + G * i];
       }
-      const double ur = (ty < 3 ? ab[NB + ty] : 0.0) * inv;
+      const double ur = (ty < NR ? ab[NB + 1 + ty] : 0.0) * inv;
       // the five inner products z and sigma^2 are made of, sum_c y_p(c) y_q(c) / d(c), are formed ONCE at the end from this log
       // (every thread used to accumulate all five in every step)
-      if (lt < 4) ylog[lt * NB + c] = (lt < 3) ? ab[NB + lt] : inv;
+      if (lt <= NR) ylog[lt * NB + c] = ab[NB + lt];
       if (MIK_MWC_LEAN(G, RI)) {  // the largest one-wavefront tiles: the row factors are read as they are used (RI fewer live doubles)
 #pragma unroll
         for (int i = cc; i < RI; ++i) {
@@ -218,7 +223,7 @@ __global__ void __launch_bounds__((G * G < 256) ? 256 : G * G, MIK_MWC_WAVES(G, 
   sync();
   double g00 = 0.0, g01 = 0.0, g11 = 0.0, g02 = 0.0, g12 = 0.0;
   for (int c = lt; c < K; c += T) {
-    const double y0 = ylog[c], y1 = ylog[NB + c], y2 = ylog[2 * NB + c], inv = ylog[3 * NB + c];
+    const double inv = ylog[c], y0 = ylog[NB + c], y1 = ylog[2 * NB + c], y2 = ylog[3 * NB + c];
     g00 += y0 * y0 * inv;
     g01 += y0 * y1 * inv;
     g11 += y1 * y1 * inv;
@@ -247,11 +252,39 @@ __global__ void __launch_bounds__((G * G < 256) ? 256 : G * G, MIK_MWC_WAVES(G, 
       }
     }
   }
+  double mu = 0.0;
   if (live && lt == 0) {
-    const double mu = (g01 - 1.0) / g11;
+    mu = (g01 - 1.0) / g11;
     a.z[pt] = g02 - mu * g12;
     a.ss[pt] = -(g00 - mu * g01) + shift - mu;
     if (bad || !(g11 > 0.0)) atomicOr(a.flag, 2);
+  }
+  // several value fields: rows 1 .. nrow - 1 give z_r = G_0r - mu G_1r, each summed and reduced in exactly the order of g02 and g12
+  // above, so that a field's z does not depend on the row it rode in
+  for (int r = 1; r < a.nrow; ++r) {
+    const double* yr = ylog + (3 + r) * NB;
+    double g0r = 0.0, g1r = 0.0;
+    for (int c = lt; c < K; c += T) {
+      const double inv = ylog[c], y0 = ylog[NB + c], y1 = ylog[2 * NB + c], y2 = yr[c];
+      g0r += y0 * y2 * inv;
+      g1r += y1 * y2 * inv;
+    }
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) {
+      g0r += __shfl_xor(g0r, o);
+      g1r += __shfl_xor(g1r, o);
+    }
+    if (T > 64) {
+      const int wv = lt >> 6;
+      __syncthreads();  // lane 0 has read the previous sums
+      if ((lt & 63) == 0) acol[2 * wv] = g0r, acol[2 * wv + 1] = g1r;
+      __syncthreads();
+      if (lt == 0) {
+        g0r = g1r = 0.0;
+        for (int q = 0; q < T / 64; ++q) g0r += acol[2 * q], g1r += acol[2 * q + 1];
+      }
+    }
+    if (live && lt == 0) a.z[pt + r * a.pstride] = g0r - mu * g1r;
   }
 }
 

@@ -96,48 +96,45 @@ static int launch_mw_chol_class(mik_handle* h, const MwArgs& a, long pc, int cls
   }
   return fail(MIK_EINVAL, "mw_class: no such LDL^T class");
 }
-template <int G, int RI>
-static int launch_mw_chol(mik_handle* h, const MwArgs& a, long pc) { return launch_mw_chol_class(h, a, pc, 100 * G + RI); }
 
-// thread-grid / register-tile classes of k_mw_chol: {G, RI} covers K <= G * RI
+// thread-grid / register-tile classes of k_mw_chol: {G, RI} covers K <= G * RI; returns 100 G + RI
 #define MIK_MW_CHOL_KMAX 256
-static int dispatch_mw_chol(mik_handle* h, const MwArgs& a, long pc) {
-  const int K = a.K;
+static int mw_chol_class(const mik_handle* h, int K) {
   if (h->opt_mw_class) {  // "mw_class" = 100 G + RI: a class forced for A/B runs (scripts/mw_classes.py)
     // (round 4: the classes that lost every A/B of rounds 2-3 -- {8,14}, {8,16}, {16,4..6}, {16,15}, {16,16}, {32,5..7} -- are no longer
     // built: each was a 100 000-instruction kernel; profiles/r03_mw_classes_*.txt keep their measurements)
-    return launch_mw_chol_class(h, a, pc, h->opt_mw_class);
+    return h->opt_mw_class;
   }
   // measured per window size (scripts/mw_classes.py, profiles/r03_mw_classes_after_kernel_changes.txt): one wavefront per point
   // as long as the register tile stays at RI <= 13 (RI = 13 only with the lean update below; beyond that the kernel needs more
   // than 256 registers and the occupancy halves: 2 x slower), then 256 threads per point up to RI = 12, 1024 threads for the last two
-  if (K <= 16) return launch_mw_chol<4, 4>(h, a, pc);    // 16 threads per point, 4 points per wavefront
+  if (K <= 16) return 100 * 4 + 4;    // 16 threads per point, 4 points per wavefront
   // round 4 (profiles/r04_mw_classes_g4.txt): 16 threads per point keep winning while the tile fits -- k = 24: {4,6} 0.37 ms per
   // 2e5 points against {8,4} 0.76; k = 32: {4,8} 0.70 / 0.93; k = 40: {4,10} 1.39 / {8,6} 1.50; k = 50: {4,13} 2.15 / {8,8} 2.54
-  if (K <= 24) return launch_mw_chol<4, 6>(h, a, pc);
-  if (K <= 32) return launch_mw_chol<4, 8>(h, a, pc);
-  if (K <= 40) return launch_mw_chol<4, 10>(h, a, pc);
-  if (K <= 48) return launch_mw_chol<8, 6>(h, a, pc);    // one wavefront per point from here to K = 104: no workgroup barrier
-  if (K <= 52) return launch_mw_chol<4, 13>(h, a, pc);
-  if (K <= 64) return launch_mw_chol<8, 8>(h, a, pc);
-  if (K <= 80) return launch_mw_chol<8, 10>(h, a, pc);
-  if (K <= 88) return launch_mw_chol<8, 11>(h, a, pc);
-  if (K <= 96) return launch_mw_chol<8, 12>(h, a, pc);
+  if (K <= 24) return 100 * 4 + 6;
+  if (K <= 32) return 100 * 4 + 8;
+  if (K <= 40) return 100 * 4 + 10;
+  if (K <= 48) return 100 * 8 + 6;    // one wavefront per point from here to K = 104: no workgroup barrier
+  if (K <= 52) return 100 * 4 + 13;
+  if (K <= 64) return 100 * 8 + 8;
+  if (K <= 80) return 100 * 8 + 10;
+  if (K <= 88) return 100 * 8 + 11;
+  if (K <= 96) return 100 * 8 + 12;
   // RI = 13 in one wavefront (round 3, second session): held to 2 wavefronts per SIMD by its launch bound, row factors read as
   // they are used (MIK_MWC_LEAN): 8 spilled registers instead of 24 AGPRs and half the occupancy -- k = 100: 10.9 ms per 2e5
   // points against 13.5 for {16,7}.  {8,14} ties with {16,7} at k = 112 (14.5 / 14.2 ms): not used.
-  if (K <= 104) return launch_mw_chol<8, 13>(h, a, pc);
-  if (K <= 112) return launch_mw_chol<16, 7>(h, a, pc);  // 256 threads per point
-  if (K <= 128) return launch_mw_chol<16, 8>(h, a, pc);
-  if (K <= 144) return launch_mw_chol<16, 9>(h, a, pc);
-  if (K <= 160) return launch_mw_chol<16, 10>(h, a, pc);
-  if (K <= 176) return launch_mw_chol<16, 11>(h, a, pc);
-  if (K <= 192) return launch_mw_chol<16, 12>(h, a, pc);
+  if (K <= 104) return 100 * 8 + 13;
+  if (K <= 112) return 100 * 16 + 7;  // 256 threads per point
+  if (K <= 128) return 100 * 16 + 8;
+  if (K <= 144) return 100 * 16 + 9;
+  if (K <= 160) return 100 * 16 + 10;
+  if (K <= 176) return 100 * 16 + 11;
+  if (K <= 192) return 100 * 16 + 12;
   // second session of round 3: RI = 13 / 14 on 256 threads, held to 2 wavefronts per SIMD (launch bound + lean update): k = 200
   // 113 -> 65 ms per 2e5 points, k = 224 123 -> 88 ms -- they replace the 1024-thread class {32,7}
-  if (K <= 208) return launch_mw_chol<16, 13>(h, a, pc);
-  if (K <= 224) return launch_mw_chol<16, 14>(h, a, pc);
-  return launch_mw_chol<32, 8>(h, a, pc);                // K <= 256: 1024 threads per point
+  if (K <= 208) return 100 * 16 + 13;
+  if (K <= 224) return 100 * 16 + 14;
+  return 100 * 32 + 8;                // K <= 256: 1024 threads per point
 }
 
 int one_predict_mw(mik_handle* h, int n_closest) {
@@ -150,12 +147,15 @@ int one_predict_mw(mik_handle* h, int n_closest) {
   MIKC(get_events(h, 2));
   const long npt = h->npt;
   const int K = n_closest;
+  const int nf = h->nf;  // value fields (mik_set_fields); 0 = the problem's values
   long solve_chunks = 0;
   h->tm.rhs_ms = h->tm.contract_ms = h->tm.predict_ms = 0.0;
   h->tm.contract_launches = 0;
   h->tm.contract_flops_executed = 0.0;
+  h->nf_done = 0;
   if (npt == 0) {
     h->have_results = true;
+    h->nf_done = nf;
     return MIK_OK;
   }
   HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));
@@ -281,116 +281,28 @@ int one_predict_mw(mik_handle* h, int n_closest) {
     sgrid = (int)g;
     MIKC(sysbuf.ensure((size_t)per * (size_t)sgrid));
   }
-  MIKC(get_events(h, 2 + 2 * (size_t)((npt + chunk - 1) / chunk)));
-  for (long p0 = 0; p0 < npt; p0 += chunk) {
-    const long pc = (npt - p0 < chunk) ? npt - p0 : chunk;
-    const unsigned kgrid = (unsigned)((pc + 255) / 256);
-    int* idx = h->mw_idx.as<int>();
-    double* dist = h->mw_dist.as<double>();
-    if (!wave_knn) {
-      if (three)
-        hipLaunchKernelGGL(k_mw_knn_big<3>, dim3(kgrid), dim3(256), 0, h->stream, qx + p0, qy + p0, qz + p0, (int)pc, sx, sy, sz,
-                           h->N, K, wd.as<double>(), wi.as<int>(), idx, dist);
-      else
-        hipLaunchKernelGGL(k_mw_knn_big<2>, dim3(kgrid), dim3(256), 0, h->stream, qx + p0, qy + p0, (const double*)nullptr,
-                           (int)pc, sx, sy, (const double*)nullptr, h->N, K, wd.as<double>(), wi.as<int>(), idx, dist);
-    } else {
-      const long wg = 32L * h->n_cu;
-      const unsigned wgrid = (unsigned)(pc < wg ? pc : wg);
-      const size_t klds = (size_t)cap * (sizeof(double) + sizeof(int));
-      KnnArgs ka{};
-      ka.px = qx + p0;
-      ka.py = qy + p0;
-      ka.pz = three ? qz + p0 : nullptr;
-      ka.npt = (int)pc;
-      ka.gx = h->grid.gx.as<double>();
-      ka.gy = h->grid.gy.as<double>();
-      ka.gz = h->grid.gz.as<double>();
-      ka.orig = h->grid.orig.as<int>();
-      ka.cstart = h->grid.cstart.as<int>();
-      ka.N = h->N, ka.K = K, ka.CAP = cap;
-      ka.nx = h->grid.nx, ka.ny = h->grid.ny, ka.nz = h->grid.nz;
-      ka.x0 = h->grid.x0, ka.y0 = h->grid.y0, ka.z0 = h->grid.z0;
-      ka.inv_cell = 1.0 / h->grid.cell;
-      ka.cell2 = h->grid.cell * h->grid.cell;
-      ka.tau0 = 0.0;
-      if (h->opt_mw_knn_bound && !h->geo && h->grid.live >= 2 && (long)h->grid.nx * h->grid.ny * h->grid.nz > 1) {
-        // radius of the disc / ball expected to hold K + 4 sqrt(K) + 2 of the ~per_cell stations a cell holds; it must stay
-        // inside the 3 x 3 (x 3) cells around the point's cell
-        const double m = K + 4.0 * std::sqrt((double)K) + 2.0, T = std::max(1.0, h->grid.per_cell);
-        const double r2 = h->grid.live == 3 ? std::pow(m / (4.18879020478639 * T), 2.0 / 3.0) : m / (3.14159265358979 * T);
-        if (r2 <= 1.0) ka.tau0 = r2 * ka.cell2;
-      }
-      ka.idx_out = idx;
-      ka.dist_out = dist;
-      // (measured, profiles/r04_mw_knn_ab.txt: rows of a grid, k = 10: search + rhs 2.65 -> 0.62 ms per 1e6 points, bit-identical; a
-      // 32-entry list per lane only ties with the wave-per-point search, and a shuffled point list sends every lane to the list --
-      // one same-address atomic per wavefront, +0.3 ms -- hence K <= 16 and the coherence test: 64 consecutive points must span
-      // few cells, judged from the median step between consecutive points that mik_set_points / mik_set_grid recorded)
-      if (h->opt_mw_knn_lane && K <= 16 && (long)h->grid.nx * h->grid.ny * h->grid.nz > 1 &&
-          (mw_sorted || (h->pts_step >= 0.0 && 64.0 * h->pts_step * (h->geo ? MIK_PI / 180.0 : 1.0) <= 10.0 * h->grid.cell))) {
-        // small windows: one lane per point over the box of cells its wavefront's 64 consecutive points share (k_mw_knn_lane); the
-        // wave-per-point kernel below then only walks the list of points that pass left unfinished
-        MIKC(todo.ensure(sizeof(int) * ((size_t)pc + 1)));
-        ka.todo_count = todo.as<int>();
-        ka.todo = todo.as<int>() + 1;
-        HIPC(hipMemsetAsync(ka.todo_count, 0, sizeof(int), h->stream));
-        const unsigned lgrid = (unsigned)std::min<long>((pc + 63) / 64, 64L * h->n_cu);
-        if (three) hipLaunchKernelGGL((k_mw_knn_lane<3, 16>), dim3(lgrid), dim3(64), 0, h->stream, ka);
-        else hipLaunchKernelGGL((k_mw_knn_lane<2, 16>), dim3(lgrid), dim3(64), 0, h->stream, ka);
-      }
-      if (three) {
-        HIPC(hipFuncSetAttribute((const void*)k_mw_knn<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)klds));
-        hipLaunchKernelGGL(k_mw_knn<3>, dim3(wgrid), dim3(64), klds, h->stream, ka);
-      } else {
-        HIPC(hipFuncSetAttribute((const void*)k_mw_knn<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)klds));
-        hipLaunchKernelGGL(k_mw_knn<2>, dim3(wgrid), dim3(64), klds, h->stream, ka);
-      }
-    }
-    if (h->geo)
-      hipLaunchKernelGGL(k_mw_geo_dist, dim3((unsigned)((pc * K + 255) / 256)), dim3(256), 0, h->stream,
-                         (const double*)h->px.as<double>() + p0, (const double*)h->py.as<double>() + p0, pc, K,
-                         (const double*)h->xs.as<double>(), (const double*)h->ys.as<double>(), (const int*)idx, dist);
-    MwArgs a{};
-    a.sx = h->xs.as<double>();
-    a.sy = h->ys.as<double>();
-    a.sz = h->zs.as<double>();
-    a.mode = h->geo ? 1 : h->ndim;
-    a.K = K;
-    a.npt = (int)pc;
-    a.idx = idx;
-    a.dist = dist;
-    a.Z = h->vals.as<double>();
-    a.v = h->v;
-    a.exact = h->exact;
-    a.eps = h->eps;
-    a.z = zout + p0;
-    a.ss = ssout + p0;
-    a.flag = h->flag.as<int>();
-    {  // right-hand sides in place over the distances
-      const long ne = pc * K;
-      const unsigned rg = (unsigned)((ne + 255) / 256);
-      if (custom) {
-        // d -> gamma(d) on the host for the point-station distances and for the K x K station pairs of every point
-        HIPC(hipMemcpyAsync(gvec.p, dist, sizeof(double) * ne, hipMemcpyDeviceToDevice, h->stream));
-        MIKC(custom_roundtrip(h, gvec.as<double>(), pc, K, K));
-        hipLaunchKernelGGL(k_mw_rhs_table, dim3(rg), dim3(256), 0, h->stream, dist, (const double*)gvec.as<double>(), ne, h->exact,
-                           h->eps);
-        hipLaunchKernelGGL(k_mw_pairdist, dim3((unsigned)((ne * K + 255) / 256)), dim3(256), 0, h->stream, (const int*)idx, pc, K,
-                           a.sx, a.sy, a.sz, a.mode, gtab.as<double>());
-        MIKC(custom_roundtrip(h, gtab.as<double>(), pc * K, K, K));
-        a.gtab = gtab.as<double>();
-      } else
-      switch (h->model) {
-        case 0: hipLaunchKernelGGL(k_mw_rhs<0>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
-        case 1: hipLaunchKernelGGL(k_mw_rhs<1>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
-        case 2: hipLaunchKernelGGL(k_mw_rhs<2>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
-        case 3: hipLaunchKernelGGL(k_mw_rhs<3>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
-        case 4: hipLaunchKernelGGL(k_mw_rhs<4>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
-        default: hipLaunchKernelGGL(k_mw_rhs<5>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
-      }
-    }
-    HIPC(hipEventRecord(h->evpool[2 + 2 * solve_chunks], h->stream));
+  // Several value fields: a point's local system does not depend on the values, so the neighbour search and the right-hand sides run once
+  // per point chunk and the fields enter only the solver -- k_mw_chol eliminates up to G - 2 of them per pass as further right-hand-side
+  // rows (the arithmetic of the single value row, hence the same bits), the other solvers take one field per launch.  The planes (npt
+  // doubles per field, twice over for sorted points) are bounded to ~2 GB by groups of fields; a group after the first repeats the
+  // search.  Plane f leaves for the page-locked landing zones (plane 0 in pin_out, the others in pin_fz) as soon as its group is done.
+  int rows = 1;  // value rows per solver pass
+  if (chol) rows = mw_chol_class(h, K) / 100 - 2;
+  int fg = 1;    // fields per group
+  const double* fv = nullptr;
+  DevBuf splanes;
+  if (nf > 0) {
+    MIKC(upload_fields(h, 0));  // the caller's station order: the neighbour lists hold the caller's station indices
+    fv = h->fv.as<double>();
+    const long per = (long)(2e9 / (8.0 * (double)npt * (mw_sorted ? 2.0 : 1.0)));
+    fg = (int)std::max(1L, std::min<long>(nf, per));
+    MIKC(h->zf.ensure(sizeof(double) * (size_t)fg * (size_t)npt));
+    if (mw_sorted) MIKC(splanes.ensure(sizeof(double) * (size_t)fg * (size_t)npt));
+    HIPC(hipEventSynchronize(h->ev_d2h));  // an earlier predict's copies may still write the landing zones
+    MIKC(h->pin_out.ensure(sizeof(double) * 2 * (size_t)npt));
+    if (nf > 1) MIKC(h->pin_fz.ensure(sizeof(double) * (size_t)(nf - 1) * (size_t)npt));
+  }
+  auto solve = [&](const MwArgs& a, long pc) -> int {
     if (big) {
       const size_t lds = sizeof(double) * 2 * (size_t)nb + sizeof(int) * (size_t)nb;
       if (lds > 150 * 1024) return fail(MIK_EINVAL, "n_closest_points too large for the device path (> ~7600)");
@@ -403,17 +315,172 @@ int one_predict_mw(mik_handle* h, int n_closest) {
       HIPC(hipFuncSetAttribute((const void*)k_mw_chol_blocked, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL(k_mw_chol_blocked, dim3(grid), dim3(256), lds, h->stream, a, sysbuf.as<double>(), cslot, ldc);
     } else if (chol) {
-      MIKC(dispatch_mw_chol(h, a, pc));
+      MIKC(launch_mw_chol_class(h, a, pc, mw_chol_class(h, K)));
     } else {
       MIKC(dispatch_mw_solve(h, a, pc));  // (always the pivoting form: valid for every window, the only one built)
     }
-    HIPC(hipEventRecord(h->evpool[3 + 2 * solve_chunks], h->stream));
-    ++solve_chunks;
-    HIPC(hipGetLastError());
+    return MIK_OK;
+  };
+  const int ngroups = nf > 0 ? (nf + fg - 1) / fg : 1;
+  MIKC(get_events(h, 2 + 2 * (size_t)ngroups * (size_t)((npt + chunk - 1) / chunk)));
+  for (int g0 = 0; g0 < std::max(nf, 1); g0 += fg) {
+    const int gn = nf > 0 ? std::min(fg, nf - g0) : 0;  // fields of this group
+    double* zpl = nf > 0 ? (mw_sorted ? splanes.as<double>() : h->zf.as<double>()) : nullptr;
+    if (g0 > 0) HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));  // the previous group's planes have left
+    for (long p0 = 0; p0 < npt; p0 += chunk) {
+      const long pc = (npt - p0 < chunk) ? npt - p0 : chunk;
+      const unsigned kgrid = (unsigned)((pc + 255) / 256);
+      int* idx = h->mw_idx.as<int>();
+      double* dist = h->mw_dist.as<double>();
+      if (!wave_knn) {
+        if (three)
+          hipLaunchKernelGGL(k_mw_knn_big<3>, dim3(kgrid), dim3(256), 0, h->stream, qx + p0, qy + p0, qz + p0, (int)pc, sx, sy, sz,
+                             h->N, K, wd.as<double>(), wi.as<int>(), idx, dist);
+        else
+          hipLaunchKernelGGL(k_mw_knn_big<2>, dim3(kgrid), dim3(256), 0, h->stream, qx + p0, qy + p0, (const double*)nullptr,
+                             (int)pc, sx, sy, (const double*)nullptr, h->N, K, wd.as<double>(), wi.as<int>(), idx, dist);
+      } else {
+        const long wg = 32L * h->n_cu;
+        const unsigned wgrid = (unsigned)(pc < wg ? pc : wg);
+        const size_t klds = (size_t)cap * (sizeof(double) + sizeof(int));
+        KnnArgs ka{};
+        ka.px = qx + p0;
+        ka.py = qy + p0;
+        ka.pz = three ? qz + p0 : nullptr;
+        ka.npt = (int)pc;
+        ka.gx = h->grid.gx.as<double>();
+        ka.gy = h->grid.gy.as<double>();
+        ka.gz = h->grid.gz.as<double>();
+        ka.orig = h->grid.orig.as<int>();
+        ka.cstart = h->grid.cstart.as<int>();
+        ka.N = h->N, ka.K = K, ka.CAP = cap;
+        ka.nx = h->grid.nx, ka.ny = h->grid.ny, ka.nz = h->grid.nz;
+        ka.x0 = h->grid.x0, ka.y0 = h->grid.y0, ka.z0 = h->grid.z0;
+        ka.inv_cell = 1.0 / h->grid.cell;
+        ka.cell2 = h->grid.cell * h->grid.cell;
+        ka.tau0 = 0.0;
+        if (h->opt_mw_knn_bound && !h->geo && h->grid.live >= 2 && (long)h->grid.nx * h->grid.ny * h->grid.nz > 1) {
+          // radius of the disc / ball expected to hold K + 4 sqrt(K) + 2 of the ~per_cell stations a cell holds; it must stay
+          // inside the 3 x 3 (x 3) cells around the point's cell
+          const double m = K + 4.0 * std::sqrt((double)K) + 2.0, T = std::max(1.0, h->grid.per_cell);
+          const double r2 = h->grid.live == 3 ? std::pow(m / (4.18879020478639 * T), 2.0 / 3.0) : m / (3.14159265358979 * T);
+          if (r2 <= 1.0) ka.tau0 = r2 * ka.cell2;
+        }
+        ka.idx_out = idx;
+        ka.dist_out = dist;
+        // (measured, profiles/r04_mw_knn_ab.txt: rows of a grid, k = 10: search + rhs 2.65 -> 0.62 ms per 1e6 points, bit-identical; a
+        // 32-entry list per lane only ties with the wave-per-point search, and a shuffled point list sends every lane to the list --
+        // one same-address atomic per wavefront, +0.3 ms -- hence K <= 16 and the coherence test: 64 consecutive points must span
+        // few cells, judged from the median step between consecutive points that mik_set_points / mik_set_grid recorded)
+        if (h->opt_mw_knn_lane && K <= 16 && (long)h->grid.nx * h->grid.ny * h->grid.nz > 1 &&
+            (mw_sorted || (h->pts_step >= 0.0 && 64.0 * h->pts_step * (h->geo ? MIK_PI / 180.0 : 1.0) <= 10.0 * h->grid.cell))) {
+          // small windows: one lane per point over the box of cells its wavefront's 64 consecutive points share (k_mw_knn_lane); the
+          // wave-per-point kernel below then only walks the list of points that pass left unfinished
+          MIKC(todo.ensure(sizeof(int) * ((size_t)pc + 1)));
+          ka.todo_count = todo.as<int>();
+          ka.todo = todo.as<int>() + 1;
+          HIPC(hipMemsetAsync(ka.todo_count, 0, sizeof(int), h->stream));
+          const unsigned lgrid = (unsigned)std::min<long>((pc + 63) / 64, 64L * h->n_cu);
+          if (three) hipLaunchKernelGGL((k_mw_knn_lane<3, 16>), dim3(lgrid), dim3(64), 0, h->stream, ka);
+          else hipLaunchKernelGGL((k_mw_knn_lane<2, 16>), dim3(lgrid), dim3(64), 0, h->stream, ka);
+        }
+        if (three) {
+          HIPC(hipFuncSetAttribute((const void*)k_mw_knn<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)klds));
+          hipLaunchKernelGGL(k_mw_knn<3>, dim3(wgrid), dim3(64), klds, h->stream, ka);
+        } else {
+          HIPC(hipFuncSetAttribute((const void*)k_mw_knn<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)klds));
+          hipLaunchKernelGGL(k_mw_knn<2>, dim3(wgrid), dim3(64), klds, h->stream, ka);
+        }
+      }
+      if (h->geo)
+        hipLaunchKernelGGL(k_mw_geo_dist, dim3((unsigned)((pc * K + 255) / 256)), dim3(256), 0, h->stream,
+                           (const double*)h->px.as<double>() + p0, (const double*)h->py.as<double>() + p0, pc, K,
+                           (const double*)h->xs.as<double>(), (const double*)h->ys.as<double>(), (const int*)idx, dist);
+      MwArgs a{};
+      a.sx = h->xs.as<double>();
+      a.sy = h->ys.as<double>();
+      a.sz = h->zs.as<double>();
+      a.mode = h->geo ? 1 : h->ndim;
+      a.K = K;
+      a.npt = (int)pc;
+      a.idx = idx;
+      a.dist = dist;
+      a.Z = h->vals.as<double>();
+      a.v = h->v;
+      a.exact = h->exact;
+      a.eps = h->eps;
+      a.z = zout + p0;
+      a.ss = ssout + p0;
+      a.flag = h->flag.as<int>();
+      a.nrow = 1;
+      a.zstride = h->N;
+      a.pstride = npt;
+      {  // right-hand sides in place over the distances
+        const long ne = pc * K;
+        const unsigned rg = (unsigned)((ne + 255) / 256);
+        if (custom) {
+          // d -> gamma(d) on the host for the point-station distances and for the K x K station pairs of every point
+          HIPC(hipMemcpyAsync(gvec.p, dist, sizeof(double) * ne, hipMemcpyDeviceToDevice, h->stream));
+          MIKC(custom_roundtrip(h, gvec.as<double>(), pc, K, K));
+          hipLaunchKernelGGL(k_mw_rhs_table, dim3(rg), dim3(256), 0, h->stream, dist, (const double*)gvec.as<double>(), ne, h->exact,
+                             h->eps);
+          hipLaunchKernelGGL(k_mw_pairdist, dim3((unsigned)((ne * K + 255) / 256)), dim3(256), 0, h->stream, (const int*)idx, pc, K,
+                             a.sx, a.sy, a.sz, a.mode, gtab.as<double>());
+          MIKC(custom_roundtrip(h, gtab.as<double>(), pc * K, K, K));
+          a.gtab = gtab.as<double>();
+        } else
+        switch (h->model) {
+          case 0: hipLaunchKernelGGL(k_mw_rhs<0>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
+          case 1: hipLaunchKernelGGL(k_mw_rhs<1>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
+          case 2: hipLaunchKernelGGL(k_mw_rhs<2>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
+          case 3: hipLaunchKernelGGL(k_mw_rhs<3>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
+          case 4: hipLaunchKernelGGL(k_mw_rhs<4>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
+          default: hipLaunchKernelGGL(k_mw_rhs<5>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
+        }
+      }
+      HIPC(hipEventRecord(h->evpool[2 + 2 * solve_chunks], h->stream));
+      if (nf == 0) {
+        MIKC(solve(a, pc));
+      } else {
+        for (int f = 0; f < gn; f += rows) {  // field g0 + f .. in the rows of one pass
+          a.nrow = std::min(rows, gn - f);
+          a.Z = fv + (size_t)(g0 + f) * (size_t)h->N;
+          a.z = zpl + (size_t)f * (size_t)npt + p0;
+          MIKC(solve(a, pc));
+        }
+      }
+      HIPC(hipEventRecord(h->evpool[3 + 2 * solve_chunks], h->stream));
+      ++solve_chunks;
+      HIPC(hipGetLastError());
+    }
+    const unsigned* perm = mw_sorted ? (const unsigned*)h->ps_idx[0].as<unsigned>() : nullptr;
+    const unsigned ugrid = (unsigned)((npt + 255) / 256);
+    if (nf == 0) {
+      if (mw_sorted)  // back to the caller's order
+        hipLaunchKernelGGL(k_ps_unsort, dim3(ugrid), dim3(256), 0, h->stream, perm, npt, (const double*)zout, (const double*)ssout, h->z.as<double>(),
+                           h->ss.as<double>());
+    } else {
+      if (mw_sorted) {  // sigma^2 and the group's planes back to the caller's order, two per launch (sigma^2 again beside an odd last plane)
+        for (int q = -1; q < gn; q += 2) {
+          const double* s0 = q < 0 ? ssout : splanes.as<double>() + (size_t)q * npt;
+          double* d0 = q < 0 ? h->ss.as<double>() : h->zf.as<double>() + (size_t)q * npt;
+          const bool pair = q + 1 < gn;
+          const double* s1 = pair ? splanes.as<double>() + (size_t)(q + 1) * npt : ssout;
+          double* d1 = pair ? h->zf.as<double>() + (size_t)(q + 1) * npt : h->ss.as<double>();
+          hipLaunchKernelGGL(k_ps_unsort, dim3(ugrid), dim3(256), 0, h->stream, perm, npt, s0, s1, d0, d1);
+        }
+      }
+      // the group's planes leave for the landing zones behind the solves
+      HIPC(hipEventRecord(h->evpool[1], h->stream));
+      HIPC(hipStreamWaitEvent(h->stream_d2h, h->evpool[1], 0));
+      for (int f = 0; f < gn; ++f) {
+        const int fi = g0 + f;
+        double* dst = fi == 0 ? h->pin_out.as<double>() : h->pin_fz.as<double>() + (size_t)(fi - 1) * npt;
+        HIPC(hipMemcpyAsync(dst, h->zf.as<double>() + (size_t)f * npt, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
+      }
+      HIPC(hipEventRecord(h->ev_d2h, h->stream_d2h));
+    }
   }
-  if (mw_sorted)  // back to the caller's order
-    hipLaunchKernelGGL(k_ps_unsort, dim3((unsigned)((npt + 255) / 256)), dim3(256), 0, h->stream, (const unsigned*)h->ps_idx[0].as<unsigned>(), npt,
-                       (const double*)zout, (const double*)ssout, h->z.as<double>(), h->ss.as<double>());
   h->tm.points_sorted = mw_sorted ? 1 : 0;
   int flag = 0;
   HIPC(hipMemcpyAsync(&flag, h->flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -437,9 +504,10 @@ int one_predict_mw(mik_handle* h, int n_closest) {
   }
   if (flag) return fail(MIK_ESINGULAR, "Singular matrix");  // cok.pyx:176-177
   MIKC(h->pin_out.ensure(sizeof(double) * 2 * (size_t)npt));
-  HIPC(hipMemcpyAsync(h->pin_out.as<double>(), h->z.p, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
+  if (nf == 0) HIPC(hipMemcpyAsync(h->pin_out.as<double>(), h->z.p, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
   HIPC(hipMemcpyAsync(h->pin_out.as<double>() + npt, h->ss.p, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
   HIPC(hipEventRecord(h->ev_d2h, h->stream_d2h));
   h->have_results = true;
+  h->nf_done = nf;
   return MIK_OK;
 }

@@ -12,7 +12,9 @@ template <int G, int RI>
 static int launch_mw_chol(hipStream_t stream, bool use_static, const MwArgs& a, long pc) {
   constexpr int T = G * G, NT = T < 256 ? 256 : T, PPB = NT / T, NB = G * RI;
   if (a.K > NB) return fail(MIK_EINVAL, "moving-window LDL^T class too small for this window");
-  const size_t lds = sizeof(double) * (size_t)(2 * (NB + 4) + 9 * NB) * PPB;
+  if (a.nrow < 1 || a.nrow > G - 2) return fail(MIK_EINVAL, "moving-window LDL^T: value rows per point out of range");
+  // per point: the two column buffers, coordinates, b, the value rows, and the log of 1 / d(c) and the eliminated right-hand sides
+  const size_t lds = sizeof(double) * (size_t)(2 * (NB + 3 + a.nrow) + (4 + a.nrow) * NB + (3 + a.nrow) * NB) * PPB;
   const dim3 grid((unsigned)((pc + PPB - 1) / PPB));
   // the variogram model as a compile-time constant where the problem allows it (Euclidean coordinates; the four models whose
   // shifted station block is positive definite and cheap): the set-up code of the kernel shrinks 20-fold (mw_entry_t)

@@ -45,13 +45,11 @@ int sort_points(mik_handle* h, long chunk, long nchunks) {
   return MIK_OK;
 }
 
-// Several value fields (mik_set_fields): C = A_inv[:, :N] V from this device's own copy of the inverse, MIK_FB columns per block of
-// k_cvec<MIK_FB> (column f is bit for bit the k_cvec of field f).  V goes up once per set of fields and station order.
-static int fields_coefficients(mik_handle* h) {
+// V in fv: field f at fv + f N, in the caller's station order (want = 0: the moving window's too) or the factor's (1)
+int upload_fields(mik_handle* h, int want) {
   // columns: a multiple of MIK_FB that also holds the last read-back launch's (fields 1 + MIK_FB k .. MIK_FB (k + 1), see launch_rhs)
   const int nf = h->nf, nfp = ((nf - 1 + MIK_FB - 1) / MIK_FB) * MIK_FB + MIK_FB;
   const long N = h->N;
-  const int want = h->factor_sorted ? 1 : 0;
   if (h->fv_sorted != want) {
     if (want && (long)h->sort_perm.size() != N) return fail(MIK_ESTATE, "mik_predict: station order of the factor unknown");
     std::vector<double> v((size_t)nfp * (size_t)N, 0.0);
@@ -69,6 +67,15 @@ static int fields_coefficients(mik_handle* h) {
     HIPC(hipStreamSynchronize(h->stream));  // v is a local
     h->fv_sorted = want;
   }
+  return MIK_OK;
+}
+
+// Several value fields (mik_set_fields): C = A_inv[:, :N] V from this device's own copy of the inverse, MIK_FB columns per block of
+// k_cvec<MIK_FB> (column f is bit for bit the k_cvec of field f).  V goes up once per set of fields and station order.
+static int fields_coefficients(mik_handle* h) {
+  const int nf = h->nf, nfp = ((nf - 1 + MIK_FB - 1) / MIK_FB) * MIK_FB + MIK_FB;
+  const long N = h->N;
+  MIKC(upload_fields(h, h->factor_sorted ? 1 : 0));
   MIKC(h->fc.ensure(sizeof(double) * (size_t)nfp * (size_t)h->Mp));
   hipLaunchKernelGGL((k_cvec<MIK_FB>), dim3((h->Mp + 3) / 4, nfp / MIK_FB), dim3(256), 0, h->stream, (const double*)h->T.as<double>(),
                      (long)h->Mp, h->M, h->N, (const double*)h->fv.as<double>(), (long)N, h->fc.as<double>(), (long)h->Mp, h->Mp);

@@ -1575,7 +1575,6 @@ int mik_predict(mik_handle* h) {
 
 int mik_predict_moving_window(mik_handle* h, int n_closest) {
   if (!h) return fail(MIK_ESTATE, "mik_predict_moving_window: NULL handle");
-  if (h->nf > 0) return fail(MIK_EINVAL, "mik_predict_moving_window: value fields are set (mik_set_fields); the moving window kriges one field");
   for (int i = 0; i <= (int)h->kids.size(); ++i) member(h, i)->nf_done = 0;
   MIKC(join_exchange(h));
   return for_each_device(h, [n_closest](int, mik_handle* d) { return one_predict_mw(d, n_closest); });

@@ -430,24 +430,32 @@ class ShardedExecutor:
         """execute_fields of the model (kriging.py) with the points sharded over the ranks: every rank factors or receives the inverse as
         execute() does, forms C = A_inv[:, :N] V from its own copy (mik_set_fields: the fields go to every rank, the factor exchange is
         unchanged) and kriges every field on its slab.  Returns (zvalues, sigmasq) as the model's execute_fields; gather="local":
-        (zvalues of the slab (F, hi - lo), sigma^2 of the slab, (lo, hi)).  No moving window."""
+        (zvalues of the slab (F, hi - lo), sigma^2 of the slab, (lo, hi)).  n_closest_points (OrdinaryKriging, OrdinaryKriging3D) as in
+        execute(): no factor and no exchange, every rank kriges the fields on its slab with the moving window."""
         m, h = self.model, self._handle
+        window = kw.pop("n_closest_points", None)
         if style not in ("grid", "masked", "points"):
             raise ValueError("style argument must be 'grid', 'points', or 'masked'")
-        m._check_backend(backend, None)
+        m._check_backend(backend, window)
         v = m._field_values(values)
+        if window is not None and int(window) > v.shape[0]:
+            raise ValueError("n_closest_points exceeds the number of stations")
         P = m._prepare(style, axes, mask, kw.get("specified_drift_arrays"), backend)
         npt, shape, fmask = P.npt, P.shape, P.mask
         lo, hi = slab_bounds(npt, self.world, self.rank)
         m._set_problem(h)
-        if self.exchange == "rccl_bcast":
-            self._factor_everywhere(h)
-        else:
-            h.factor()
-        P.load(h, m._ndim, cell_range=(lo, hi - lo))
+        if window is None:
+            if self.exchange == "rccl_bcast":
+                self._factor_everywhere(h)
+            else:
+                h.factor()
+        P.load(h, m._ndim, cell_range=(lo, hi - lo), with_extra=window is None)
         h.set_fields(v.T)
         try:
-            h.predict()
+            if window is None:
+                h.predict()
+            else:
+                h.predict_moving_window(int(window))
             z, ss = h.get_field_results(), h.get_results()[1]
         finally:
             h.set_fields(None)

@@ -658,7 +658,12 @@ class _KrigingBase:
         (drifts, anisotropy, exact_values, pseudo_inv, coordinates_type, custom callables) -- not what F objects that each fit
         their own variogram would give.  sigma^2 does not depend on the values and is computed once.  The matrix, its inverse,
         the right-hand sides and sigma^2 are shared by the fields, so F fields cost little more than one ``execute()``.
-        There is no moving window (n_closest_points) here."""
+
+        ``OrdinaryKriging`` and ``OrdinaryKriging3D`` also take ``n_closest_points`` (the moving window) with the argument rules of
+        their ``execute()``: ``zvalues[f]`` is then bit for bit ``execute(..., n_closest_points=k)`` of such a per-field object, and
+        ``sigmasq`` that of this object.  A point's local system does not depend on the values: the neighbour search, the local
+        right-hand sides and, for windows up to 256, the factorisation of each local system are shared by up to G - 2 fields per pass
+        (G = 4, 8, 16 or 32 with the window).  The universal-kriging classes have no moving window, as in their ``execute()``."""
 
     def _field_values(self, values):
         n = int(np.size(self._values()))
@@ -675,20 +680,34 @@ class _KrigingBase:
             raise ValueError("values holds non-finite entries")
         return v
 
-    def _execute_fields(self, style, axes, values, mask, backend, prepare_kw):
+    def _execute_fields(self, style, axes, values, mask, backend, prepare_kw, n_closest_points=None):
         """execute_fields of the four classes: every argument is checked on the host before the device is touched."""
         if style != "grid" and style != "masked" and style != "points":
             raise ValueError("style argument must be 'grid', 'points', or 'masked'")
-        self._check_backend(backend, None)
+        self._check_backend(backend, n_closest_points)
         v = self._field_values(values)
+        if n_closest_points is not None and int(n_closest_points) > v.shape[0]:
+            raise ValueError("n_closest_points exceeds the number of stations")  # what mik_predict_moving_window answers execute()
         P = self._prepare(style, axes, mask, **prepare_kw)
-        h = self._upload_and_factor()
+        if n_closest_points is None:
+            h = self._upload_and_factor()
+        else:  # _solve_moving_window's set-up: no factor
+            h = self._get_handle()
+            self._set_problem(h)
         self._max_points = max(self._max_points, int(np.prod(P.shape)))
         self._max_fields = max(self._max_fields, v.shape[1])
-        P.load(h, self._ndim)
+        P.load(h, self._ndim, with_extra=n_closest_points is None)
         h.set_fields(v.T)
         try:
-            h.predict()
+            if n_closest_points is None:
+                h.predict()
+            else:
+                try:
+                    h.predict_moving_window(int(n_closest_points))
+                except np.linalg.LinAlgError as e:
+                    if backend == "C":  # as _solve_moving_window
+                        raise ValueError("Singular matrix") from e
+                    raise
             self.last_timing = h.timing()
             zf = h.get_field_results()  # (before get_results: that one may take the landing zone over)
             _, ss = h.get_results()
@@ -818,8 +837,8 @@ class OrdinaryKriging(_KrigingBase):
             z, ss = self._solve(P)
         return self._finish(z, ss, style, P.shape, P.mask, backend)
 
-    def execute_fields(self, style, xpoints, ypoints, values, mask=None, backend="vectorized"):
-        return self._execute_fields(style, (xpoints, ypoints), values, mask, backend, {})
+    def execute_fields(self, style, xpoints, ypoints, values, mask=None, backend="vectorized", n_closest_points=None):
+        return self._execute_fields(style, (xpoints, ypoints), values, mask, backend, {}, n_closest_points)
 
     execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
 
@@ -1062,8 +1081,8 @@ class OrdinaryKriging3D(_KrigingBase):
             z, ss = self._solve(P)
         return self._finish(z, ss, style, P.shape, P.mask, backend)
 
-    def execute_fields(self, style, xpoints, ypoints, zpoints, values, mask=None, backend="vectorized"):
-        return self._execute_fields(style, (xpoints, ypoints, zpoints), values, mask, backend, {})
+    def execute_fields(self, style, xpoints, ypoints, zpoints, values, mask=None, backend="vectorized", n_closest_points=None):
+        return self._execute_fields(style, (xpoints, ypoints, zpoints), values, mask, backend, {}, n_closest_points)
 
     execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
 
