@@ -36,11 +36,12 @@ extern "C" {
  *   4 -> 5  mik_grid.cell_count == 0 is an EMPTY range (it used to mean "the whole grid", which is now -1): a caller that
  *           zero-initialises mik_grid must set cell_count = -1.  mik_abi_version() returns the library's value; the Python
  *           loader (pykrige_amd/_lib.py) refuses a library whose version differs from the header it was written against. */
-#define MIK_ABI_VERSION 8
+#define MIK_ABI_VERSION 9
 /*   5 -> 6  mik_timing grew by sparse_ktile + reserved2 (8 bytes appended; earlier fields unchanged). */
 /*   6 -> 7  mik_timing grew by exchange_bytes (8 bytes appended); the factor exchange moves the packed upper block triangle of the inverse
  *           (option "exchange_tri"); the option keys of the experiments of rounds 2-5 are refused (see the option list). */
 /*   7 -> 8  mik_predict_moving_window kriges the value fields of mik_set_fields (it returned MIK_EINVAL with fields set). */
+/*   8 -> 9  mik_cross_validate added. */
 
 #define MIK_OK          0
 #define MIK_EINVAL     (-1) /* bad argument            -> Python ValueError                  */
@@ -372,6 +373,22 @@ int  mik_synchronize(mik_handle *h);                       /* wait until the han
  * (no mik_factor: each point solves its own (k+1)x(k+1) system).  Results as for mik_predict; with value fields set
  * (mik_set_fields) every field is kriged, see there. */
 int  mik_predict_moving_window(mik_handle *h, int n_closest_points);
+
+/* Leave-one-out cross-validation on the device: entry i is station i kriged from the OTHER stations with the problem's variogram, drift
+ * terms and exact_values.  zhat_out holds max(nf, 1) planes of n doubles -- the fields of mik_set_fields if they are set (plane f = field f),
+ * else the problem's values --, ss_out n doubles (sigma^2 does not depend on the values), both in the station order of mik_problem.  Needs
+ * mik_set_problem only.
+ *   n_closest_points = 0 (global form): from ALL other stations.  The kriging matrix has a zero diagonal, so with B = A^-1 and
+ *     c = B[:, :n] v the block inverse gives  zhat_i = v_i - c_i / B_ii,  sigma^2_i = 1 / B_ii  -- for ordinary and universal kriging alike,
+ *     drift and border rows included: all n predictions of all fields cost the factor, one pass over the station rows of the inverse
+ *     (k_cvec<8> with a diagonal epilogue: plane f is bit for bit the one-field result) and one copy back.  Factors if no factor is resident
+ *     (a resident one is reused, like mik_predict); runs on the handle's own device (a device group's members take no part).  B_ii is used as
+ *     computed: a zero or non-finite B_ii gives IEEE inf / nan in that entry, nothing is raised.  MIK_EINVAL with pseudo_inv: the identity
+ *     needs a regular inverse.
+ *   n_closest_points != 0 (windowed form: from the k nearest other stations) is not built: MIK_EINVAL, nothing is computed in its place.
+ * The resident points and the results of an earlier predict stay as they are (mik_get_results / mik_get_field_results / mik_take_results
+ * still return them, also when this call factors). */
+int  mik_cross_validate(mik_handle *h, int n_closest_points /* 0 = global */, double *zhat_out /* nf x n */, double *ss_out /* n */);
 
 /* Variogram-fit statistics: replaces core._find_statistics -> core._krige (core.py:759-836, 654-756): for
  * i = 1..n-1 station i is kriged from stations 0..i-1.  k_out / ss_out have n entries (entry 0 unused = 0). */

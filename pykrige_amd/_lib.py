@@ -69,7 +69,7 @@ class MikTiming(C.Structure):
 
 
 _lib = None
-ABI_VERSION = 8  # include/mikrige.h MIK_ABI_VERSION
+ABI_VERSION = 9  # include/mikrige.h MIK_ABI_VERSION
 
 # every entry point include/mikrige.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -98,6 +98,7 @@ SIGNATURES = {
     "mik_synchronize": (C.c_int, [C.c_void_p]),
     "mik_set_custom_variogram": (C.c_int, [C.c_void_p, VARIOGRAM_FN, C.c_void_p]),
     "mik_predict_moving_window": (C.c_int, [C.c_void_p, C.c_int]),
+    "mik_cross_validate": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "mik_statistics": (C.c_int, [C.c_void_p, _dp, _dp]),
     "mik_experimental_variogram": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int32)]),
     "mik_krige_execute": (C.c_int, [C.c_int, C.POINTER(MikProblem), C.POINTER(MikPoints), _dp, _dp]),
@@ -249,6 +250,7 @@ class Handle:
         if not (xs.size == ys.size == values.size) or (zs is not None and zs.size != xs.size):
             raise ValueError("station arrays must have the same length")
         p.ndim, p.model_id, p.n = int(ndim), int(model_id), xs.size
+        self._n, self._fields = int(xs.size), None  # (mik_set_problem clears the fields)
         p.xs, p.ys, p.zs, p.values = _ptr(xs), _ptr(ys), _ptr(zs), _ptr(values)
         pr = list(params) + [0.0] * (3 - len(params))
         if int(model_id) == 0:  # linear [slope, nugget]
@@ -360,6 +362,16 @@ class Handle:
     def predict_moving_window(self, n_closest_points):
         self._taken = None
         check(self._lib.mik_predict_moving_window(self._h, int(n_closest_points)))
+
+    def cross_validate(self, n_closest_points=0):
+        """mik_cross_validate: station i kriged from all other stations, read off the resident inverse (n_closest_points = 0, the only form
+        built; the library factors first if no factor is resident).  Returns (zhat, sigma^2): (nf, n) for the fields of set_fields -- (1, n)
+        for the problem's values without -- and (n,), in the caller's station order.  The resident points and results stay as they are."""
+        n = self._n
+        zhat = np.empty((getattr(self, "_fields", None) or 1, n), dtype=np.float64)
+        ss = np.empty(n, dtype=np.float64)
+        check(self._lib.mik_cross_validate(self._h, int(n_closest_points), _ptr(zhat), _ptr(ss)))
+        return zhat, ss
 
     def statistics(self, n):
         k = np.zeros(n, dtype=np.float64)

@@ -1,6 +1,6 @@
 // mik_k_fields.h -- several value fields on one station set (mik_set_fields): the coefficient block C = A_inv[:, :N] V and the
 // z sums of the fields after the first, read back from the right-hand-side panel k_rhs has just written.
-// Included by mik_k_predict.h (after RhsArgs); the kernels are an overload of k_cvec and instantiations of k_rhs, no new names.
+// Included by mik_k_predict.h (after RhsArgs); the kernels are overloads of k_cvec and instantiations of k_rhs, no new names.
 #pragma once
 #include "mik_dev.h"
 
@@ -36,6 +36,39 @@ __global__ void __launch_bounds__(256) k_cvec(const double* __restrict__ Ainv, l
   if (lane == 0) {
 #pragma unroll
     for (int f = 0; f < FB; ++f) C[(f0 + f) * ldc + row] = s[f];
+  }
+}
+
+// Leave-one-out cross-validation from the inverse (mik_cross_validate, global form): the kriging matrix has a zero diagonal, so the block
+// inverse gives station i kriged from all the others as zhat_i = v_i - c_i / B_ii with sigma^2_i = 1 / B_ii, B = A_inv and c = B[:, :N] v --
+// ordinary and universal kriging alike (the drift and border rows belong to "the others").  The sums are the overload's above (same lanes,
+// same butterfly), so plane f is bit for bit the one-field result; the epilogue of a station row reads B[row][row] and V[f][row] and writes
+// zhat (plane stride ldz) and, from the first block of fields, 1 / B_ii.  B_ii is used as computed: zero or non-finite gives IEEE inf / nan.
+template <int FB>
+__global__ void __launch_bounds__(256) k_cvec(const double* __restrict__ Ainv, long ld, int N, const double* __restrict__ V, long ldv,
+                                              double* __restrict__ zhat, long ldz, double* __restrict__ ss) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const long f0 = (long)blockIdx.y * FB;
+  if (row >= N) return;
+  double s[FB];
+#pragma unroll
+  for (int f = 0; f < FB; ++f) s[f] = 0.0;
+  const double* r = Ainv + (long)row * ld;
+  const double* v = V + f0 * ldv;
+  for (int j = lane; j < N; j += 64) {
+    const double a = r[j];
+#pragma unroll
+    for (int f = 0; f < FB; ++f) s[f] += a * v[f * ldv + j];
+  }
+#pragma unroll
+  for (int f = 0; f < FB; ++f)
+    for (int o = 32; o > 0; o >>= 1) s[f] += __shfl_xor(s[f], o);
+  if (lane == 0) {
+    const double bii = r[row];
+#pragma unroll
+    for (int f = 0; f < FB; ++f) zhat[(f0 + f) * ldz + row] = v[f * ldv + row] - s[f] / bii;
+    if (blockIdx.y == 0) ss[row] = 1.0 / bii;
   }
 }
 

@@ -83,6 +83,53 @@ static int fields_coefficients(mik_handle* h) {
   return MIK_OK;
 }
 
+// Leave-one-out cross-validation from the resident inverse (mik_cross_validate, global form): one launch of the k_cvec<MIK_FB> overload with the
+// diagonal epilogue over the station rows -- the fields of mik_set_fields, else the problem's values, in the factor's station order -- then
+// one copy back and, for a factor in Hilbert-curve order, the un-permutation on the host.  Touches neither the resident points nor results.
+// zhat_out: max(nf, 1) planes of N in the caller's station order; ss_out: N.
+int one_cross_validate(mik_handle* h, double* zhat_out, double* ss_out) {
+  if (!h->have_factor) return fail(MIK_ESTATE, "mik_cross_validate: no factor");
+  if (h->pinv) return fail(MIK_EINVAL, "mik_cross_validate: the leave-one-out identity needs a regular inverse (pseudo_inv is set)");
+  HIPC(hipSetDevice(h->device));
+  const long N = h->N;
+  const int nf = std::max(h->nf, 1), nfp = ((nf + MIK_FB - 1) / MIK_FB) * MIK_FB;
+  const bool sorted = h->factor_sorted;
+  if (sorted && (long)h->sort_perm.size() != N) return fail(MIK_ESTATE, "mik_cross_validate: station order of the factor unknown");
+  std::vector<double> v((size_t)nfp * (size_t)N, 0.0);
+  for (int f = 0; f < nf; ++f) {
+    const double* src = h->nf > 0 ? h->hfields.data() + (size_t)f * N : h->hvals.data();
+    double* dst = v.data() + (size_t)f * N;
+    if (sorted) {
+      for (long i = 0; i < N; ++i) dst[i] = src[h->sort_perm[(size_t)i]];
+    } else {
+      memcpy(dst, src, sizeof(double) * (size_t)N);
+    }
+  }
+  DevBuf dv, dout;  // V (padded to a multiple of MIK_FB fields); the zhat planes and 1 / B_ii behind them.  Freed after the stream drained
+  MIKC(dv.ensure(sizeof(double) * v.size()));
+  MIKC(dout.ensure(sizeof(double) * (size_t)(nfp + 1) * (size_t)N));
+  HIPC(hipMemcpyAsync(dv.p, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, h->stream));
+  double* zd = dout.as<double>();
+  double* sd = zd + (size_t)nfp * (size_t)N;
+  hipLaunchKernelGGL((k_cvec<MIK_FB>), dim3((unsigned)((N + 3) / 4), nfp / MIK_FB), dim3(256), 0, h->stream, (const double*)h->T.as<double>(),
+                     (long)h->Mp, (int)N, (const double*)dv.as<double>(), N, zd, N, sd);
+  HIPC(hipGetLastError());
+  std::vector<double> out((size_t)(nf + 1) * (size_t)N);
+  HIPC(hipMemcpyAsync(out.data(), zd, sizeof(double) * (size_t)nf * (size_t)N, hipMemcpyDeviceToHost, h->stream));
+  HIPC(hipMemcpyAsync(out.data() + (size_t)nf * N, sd, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
+  HIPC(hipStreamSynchronize(h->stream));
+  for (int f = 0; f <= nf; ++f) {
+    const double* src = out.data() + (size_t)f * N;
+    double* dst = f < nf ? zhat_out + (size_t)f * N : ss_out;
+    if (sorted) {
+      for (long i = 0; i < N; ++i) dst[h->sort_perm[(size_t)i]] = src[i];
+    } else {
+      memcpy(dst, src, sizeof(double) * (size_t)N);
+    }
+  }
+  return MIK_OK;
+}
+
 // point blocks per group of k_sp_tiles_g's queue order (a group's tiles run on one XCD, tile position ascending, point block fast;
 // round 5: 4 -> 16, contraction 35.7 -> 35.3 ms at config 5)
 static constexpr int SP_GROUP = 16;

@@ -725,6 +725,53 @@ class _KrigingBase:
             zf = np.ma.array(zf, mask=np.zeros(zf.shape, dtype=bool))
         return zf.reshape((nf,) + tuple(shape)), ss
 
+    # ---------------------------------------------------------------- leave-one-out cross-validation (mik_cross_validate)
+    _CV_DOC = """Leave-one-out cross-validation on the device: every station kriged from the other stations.
+
+        ``zhat, sigmasq = obj.cross_validate(values=None, n_closest_points=None, backend="vectorized")``
+
+        ``values`` is ``None`` (the object's own values), ``(N,)`` or ``(N, F)`` (F fields measured at the stations, as in
+        ``execute_fields``).  ``zhat`` has shape ``(N,)`` for ``None`` or 1-D values and ``(F, N)`` for 2-D values; ``sigmasq`` has
+        shape ``(N,)`` and does not depend on the values.  Both are plain float64 ndarrays in the order the stations were given in.
+        The residuals are ``values - zhat``.  The variogram, the drift terms, the anisotropy and ``exact_values`` are the object's; the
+        variogram is not fitted again without station i.
+
+        Global form (``n_closest_points=None``): entry i is station i kriged from ALL other stations.  The kriging matrix has a zero
+        diagonal, so with ``B`` its inverse and ``c = B[:, :N] v`` the block inverse gives ``zhat_i = v_i - c_i / B_ii`` and
+        ``sigmasq_i = 1 / B_ii`` exactly, for ordinary and universal kriging alike (drift and border rows included): all N predictions
+        of all F fields cost the one factorisation ``execute()`` needs anyway (and reuses), one pass over the inverse and a
+        diagonal read.  ``exact_values`` plays no part (no other station lies within eps of station i unless it is a duplicate, and
+        duplicated stations make the matrix singular).  ``B_ii`` is used as computed: a zero or non-finite one gives inf / nan in
+        that entry and nothing is raised.  An object with ``pseudo_inv=True`` raises ``ValueError``: the identity needs a regular
+        inverse.  Runs on the handle's own device; a device group takes no share in it.
+
+        Windowed form (``n_closest_points=k``: station i kriged from its k nearest other stations): not built.  The argument is
+        checked by the backend rules of ``execute()`` (the universal-kriging classes raise as for any moving window) and the call then
+        raises ``NotImplementedError``; nothing else is computed in its place.
+
+        The points and results an earlier ``execute()`` left on the device stay as they are."""
+
+    def cross_validate(self, values=None, n_closest_points=None, backend="vectorized"):
+        self._check_backend(backend, n_closest_points)
+        v = None if values is None else self._field_values(values)
+        if n_closest_points is not None:
+            raise NotImplementedError("cross_validate: the windowed form (n_closest_points) is not built; n_closest_points=None kriges "
+                                      "every station from all other stations")
+        if self.pseudo_inv:
+            raise ValueError("cross_validate needs a regular inverse: the leave-one-out identity does not hold for pseudo_inv=True")
+        h = self._upload_and_factor()
+        if v is not None:
+            self._max_fields = max(self._max_fields, v.shape[1])
+            h.set_fields(v.T)
+        try:
+            zhat, ss = h.cross_validate(0)
+        finally:
+            if v is not None:
+                h.set_fields(None)
+        return (zhat if v is not None and np.ndim(values) == 2 else zhat[0]), ss
+
+    cross_validate.__doc__ = _CV_DOC
+
     def _spec_rows(self, style, shape, npt, specified_drift_arrays):
         """uk.py:1217-1274 / uk3d.py:1030-1095: validate + flatten the per-point specified-drift arrays."""
         if specified_drift_arrays is None:
