@@ -390,6 +390,21 @@ int  mik_predict_moving_window(mik_handle *h, int n_closest_points);
  * still return them, also when this call factors). */
 int  mik_cross_validate(mik_handle *h, int n_closest_points /* 0 = global */, double *zhat_out /* nf x n */, double *ss_out /* n */);
 
+/* Leave-group-out (k-fold) cross-validation from the same inverse: fold[i] in [0, nfolds) names the group of station i (station order of
+ * mik_problem); every group S is kriged from all stations outside it.  With B = A^-1, c = B[:, :n] v and R = everything else (border and drift
+ * rows included) the block inverse gives  B_SS^-1 = A_SS - A_SR A_RR^-1 A_RS  and hence
+ *     zhat_S = v_S - B_SS^-1 c_S,   sigma^2_S = diag(B_SS^-1)
+ * exactly, for ordinary and universal kriging alike; a group of one station is mik_cross_validate's formula.  c is k_cvec<8>'s (leave-one-out's
+ * sums); each group then costs one workgroup: gather B[S, S], Cholesky, triangular inverse, two triangular products per block of eight fields
+ * (k_cvec<8, BIG>, mik_k_cvfolds.h: groups of up to 96 stations in LDS, larger ones in 64-column panels of m x m doubles of scratch).  Plane f
+ * is bit for bit the one-field result, and a group's results depend on its members alone, not on its index.  A group whose block is not
+ * numerically positive definite (non-positive or non-finite pivot) gets NaN in zhat and sigma^2; the others are unaffected, nothing is raised.
+ * MIK_EINVAL: an index outside [0, nfolds), a group that holds every station, pseudo_inv.  Empty groups are allowed.  Otherwise the rules of
+ * mik_cross_validate: factors if no factor is resident (a resident one is reused), runs on the handle's own device, uses the fields of
+ * mik_set_fields or else the problem's values, leaves the resident points and the results of an earlier predict as they are.
+ * (Added without a new ABI version: no existing signature or field changed.) */
+int  mik_cross_validate_folds(mik_handle *h, const int32_t *fold /* n */, int nfolds, double *zhat_out /* nf x n */, double *ss_out /* n */);
+
 /* Variogram-fit statistics: replaces core._find_statistics -> core._krige (core.py:759-836, 654-756): for
  * i = 1..n-1 station i is kriged from stations 0..i-1.  k_out / ss_out have n entries (entry 0 unused = 0). */
 int  mik_statistics(mik_handle *h, double *k_out, double *ss_out);

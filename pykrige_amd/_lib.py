@@ -70,6 +70,7 @@ class MikTiming(C.Structure):
 
 _lib = None
 ABI_VERSION = 9  # include/mikrige.h MIK_ABI_VERSION
+CV_FOLDS_LDS = 96  # csrc/mik_k_cvfolds.h MIK_CVF_LDS: the largest fold mik_cross_validate_folds factors in LDS (larger ones: 64-column panels)
 
 # every entry point include/mikrige.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -99,6 +100,7 @@ SIGNATURES = {
     "mik_set_custom_variogram": (C.c_int, [C.c_void_p, VARIOGRAM_FN, C.c_void_p]),
     "mik_predict_moving_window": (C.c_int, [C.c_void_p, C.c_int]),
     "mik_cross_validate": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "mik_cross_validate_folds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, _dp, _dp]),
     "mik_statistics": (C.c_int, [C.c_void_p, _dp, _dp]),
     "mik_experimental_variogram": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int32)]),
     "mik_krige_execute": (C.c_int, [C.c_int, C.POINTER(MikProblem), C.POINTER(MikPoints), _dp, _dp]),
@@ -371,6 +373,19 @@ class Handle:
         zhat = np.empty((getattr(self, "_fields", None) or 1, n), dtype=np.float64)
         ss = np.empty(n, dtype=np.float64)
         check(self._lib.mik_cross_validate(self._h, int(n_closest_points), _ptr(zhat), _ptr(ss)))
+        return zhat, ss
+
+    def cross_validate_folds(self, fold, nfolds):
+        """mik_cross_validate_folds: every group of stations kriged from the stations outside it, from the resident inverse.  fold: (n,) integers
+        in [0, nfolds), the group of each station in the caller's order.  Returns (zhat, sigma^2) shaped as cross_validate's; a group whose block
+        of the inverse is not positive definite holds NaN.  The resident points and results stay as they are."""
+        n = self._n
+        fold = np.ascontiguousarray(fold, dtype=np.int32)
+        if fold.shape != (n,):
+            raise ValueError("fold must have shape (%d,)" % n)
+        zhat = np.empty((getattr(self, "_fields", None) or 1, n), dtype=np.float64)
+        ss = np.empty(n, dtype=np.float64)
+        check(self._lib.mik_cross_validate_folds(self._h, fold.ctypes.data_as(C.POINTER(C.c_int32)), int(nfolds), _ptr(zhat), _ptr(ss)))
         return zhat, ss
 
     def statistics(self, n):

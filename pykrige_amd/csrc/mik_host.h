@@ -501,6 +501,7 @@ int upload_fields(mik_handle* h, int want);                                     
 int one_predict(mik_handle* h);                                                                                  // mik_predict.hip
 int one_predict_mw(mik_handle* h, int n_closest);
 int one_cross_validate(mik_handle* h, double* zhat_out, double* ss_out);                                         // mik_predict.hip
+int one_cross_validate_folds(mik_handle* h, const int32_t* fold, int nfolds, double* zhat_out, double* ss_out);  // mik_predict.hip
 // mik_mw_chol.hip, part N: launches class 100 G + RI of k_mw_chol if it holds it, else returns MIK_MWC_NOCLASS
 #define MIK_MWC_PARTS 5
 #define MIK_MWC_NOCLASS (-9999)

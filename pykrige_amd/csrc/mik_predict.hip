@@ -130,6 +130,106 @@ int one_cross_validate(mik_handle* h, double* zhat_out, double* ss_out) {
   return MIK_OK;
 }
 
+// Leave-group-out cross-validation from the resident inverse (mik_cross_validate_folds): fold[i] in [0, nfolds) is the group of caller
+// station i; every group is kriged from all the others (mik_k_cvfolds.h).  The per-fold station lists are built in the FACTOR's station
+// order (a Hilbert-ordered factor holds caller station sort_perm[p] at position p), ascending, so that a fold's sums depend on its members
+// alone.  c = B[:, :N] V by the coefficient overload of k_cvec<MIK_FB> (leave-one-out's sums), then one launch per size class: folds of
+// up to MIK_CVF_LDS stations factor their block in LDS, larger ones in m x m doubles of scratch (sum of m^2 over those folds, at most N^2,
+// one allocation with the two work planes, freed after the stream drained).  Copy back and un-permutation as one_cross_validate.
+int one_cross_validate_folds(mik_handle* h, const int32_t* fold, int nfolds, double* zhat_out, double* ss_out) {
+  if (!h->have_factor) return fail(MIK_ESTATE, "mik_cross_validate_folds: no factor");
+  if (h->pinv) return fail(MIK_EINVAL, "mik_cross_validate_folds: the block-inverse identity needs a regular inverse (pseudo_inv is set)");
+  HIPC(hipSetDevice(h->device));
+  const long N = h->N;
+  const int nf = std::max(h->nf, 1), nfp = ((nf + MIK_FB - 1) / MIK_FB) * MIK_FB;
+  const bool sorted = h->factor_sorted;
+  if (sorted && (long)h->sort_perm.size() != N) return fail(MIK_ESTATE, "mik_cross_validate_folds: station order of the factor unknown");
+  std::vector<long> off((size_t)nfolds + 1, 0);
+  for (long i = 0; i < N; ++i) {
+    if (fold[i] < 0 || fold[i] >= nfolds) return fail(MIK_EINVAL, "mik_cross_validate_folds: fold index outside [0, nfolds)");
+    ++off[(size_t)fold[i] + 1];
+  }
+  for (int f = 0; f < nfolds; ++f) {
+    if (off[(size_t)f + 1] >= N) return fail(MIK_EINVAL, "mik_cross_validate_folds: a fold holds every station (nothing is left to krige from)");
+    off[(size_t)f + 1] += off[(size_t)f];
+  }
+  std::vector<int> idx((size_t)N);
+  {
+    std::vector<long> fill(off.begin(), off.end() - 1);
+    for (long p = 0; p < N; ++p) idx[(size_t)fill[(size_t)fold[sorted ? h->sort_perm[(size_t)p] : p]]++] = (int)p;
+  }
+  // the two launches' descriptors (first entry of idx, m, first double in scratch), small folds first; empty folds take no part
+  std::vector<long> desc;
+  int nsmall = 0, nbig = 0, msmall = 0;
+  size_t gtot = 0;
+  for (int big = 0; big < 2; ++big)
+    for (int f = 0; f < nfolds; ++f) {
+      const long m = off[(size_t)f + 1] - off[(size_t)f];
+      if (m == 0 || (m > MIK_CVF_LDS) != (big == 1)) continue;
+      desc.insert(desc.end(), {off[(size_t)f], m, (long)gtot});
+      if (big) {
+        gtot += (size_t)m * (size_t)m;
+        ++nbig;
+      } else {
+        msmall = std::max(msmall, (int)m);
+        ++nsmall;
+      }
+    }
+  std::vector<double> v((size_t)nfp * (size_t)N, 0.0);
+  for (int f = 0; f < nf; ++f) {
+    const double* src = h->nf > 0 ? h->hfields.data() + (size_t)f * N : h->hvals.data();
+    double* dst = v.data() + (size_t)f * N;
+    if (sorted) {
+      for (long i = 0; i < N; ++i) dst[i] = src[h->sort_perm[(size_t)i]];
+    } else {
+      memcpy(dst, src, sizeof(double) * (size_t)N);
+    }
+  }
+  // V and c (nfp planes each); zhat (nfp planes) and sigma^2; scratch and the two work planes; the lists.  Freed after the stream drained
+  DevBuf dv, dout, dwork, dlist;
+  MIKC(dv.ensure(sizeof(double) * 2 * v.size()));
+  MIKC(dout.ensure(sizeof(double) * (size_t)(nfp + 1) * (size_t)N));
+  MIKC(dwork.ensure(sizeof(double) * (gtot + 2 * (size_t)MIK_FB * (size_t)N)));
+  MIKC(dlist.ensure(sizeof(long) * desc.size() + sizeof(int) * idx.size()));
+  HIPC(hipMemcpyAsync(dv.p, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, h->stream));
+  HIPC(hipMemcpyAsync(dlist.p, desc.data(), sizeof(long) * desc.size(), hipMemcpyHostToDevice, h->stream));
+  int* didx = reinterpret_cast<int*>(dlist.as<long>() + desc.size());
+  HIPC(hipMemcpyAsync(didx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice, h->stream));
+  double* cd = dv.as<double>() + v.size();
+  hipLaunchKernelGGL((k_cvec<MIK_FB>), dim3((unsigned)((N + 3) / 4), nfp / MIK_FB), dim3(256), 0, h->stream, (const double*)h->T.as<double>(),
+                     (long)h->Mp, (int)N, (int)N, (const double*)dv.as<double>(), N, cd, N, (int)N);
+  CvfArgs a;
+  a.B = h->T.as<double>(), a.ldb = h->Mp, a.C = cd, a.V = dv.as<double>(), a.idx = didx, a.desc = dlist.as<long>();
+  a.scratch = dwork.as<double>(), a.wc = a.scratch + gtot, a.wt = a.wc + (size_t)MIK_FB * (size_t)N;
+  a.zhat = dout.as<double>(), a.ss = a.zhat + (size_t)nfp * (size_t)N, a.n = N, a.nfb = nfp / MIK_FB, a.ldw = msmall | 1;
+  if (nsmall) {
+    const size_t lds = sizeof(double) * (size_t)msmall * (size_t)a.ldw;
+    HIPC(hipFuncSetAttribute((const void*)k_cvec<MIK_FB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_cvec<MIK_FB, false>), dim3((unsigned)nsmall), dim3(256), lds, h->stream, a);
+  }
+  if (nbig) {
+    const size_t lds = sizeof(double) * 2 * MIK_CVF_NB * MIK_CVF_TLD;
+    a.desc += 3 * (size_t)nsmall;
+    HIPC(hipFuncSetAttribute((const void*)k_cvec<MIK_FB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_cvec<MIK_FB, true>), dim3((unsigned)nbig), dim3(256), lds, h->stream, a);
+  }
+  HIPC(hipGetLastError());
+  std::vector<double> out((size_t)(nf + 1) * (size_t)N);
+  HIPC(hipMemcpyAsync(out.data(), a.zhat, sizeof(double) * (size_t)nf * (size_t)N, hipMemcpyDeviceToHost, h->stream));
+  HIPC(hipMemcpyAsync(out.data() + (size_t)nf * N, a.ss, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
+  HIPC(hipStreamSynchronize(h->stream));
+  for (int f = 0; f <= nf; ++f) {
+    const double* src = out.data() + (size_t)f * N;
+    double* dst = f < nf ? zhat_out + (size_t)f * N : ss_out;
+    if (sorted) {
+      for (long i = 0; i < N; ++i) dst[h->sort_perm[(size_t)i]] = src[i];
+    } else {
+      memcpy(dst, src, sizeof(double) * (size_t)N);
+    }
+  }
+  return MIK_OK;
+}
+
 // point blocks per group of k_sp_tiles_g's queue order (a group's tiles run on one XCD, tile position ascending, point block fast;
 // round 5: 4 -> 16, contraction 35.7 -> 35.3 ms at config 5)
 static constexpr int SP_GROUP = 16;

@@ -1580,22 +1580,38 @@ int mik_predict_moving_window(mik_handle* h, int n_closest) {
   return for_each_device(h, [n_closest](int, mik_handle* d) { return one_predict_mw(d, n_closest); });
 }
 
+// The factor of the cross-validation entry points: a resident one is reused, else mik_factor runs -- and the results of an earlier predict stay.
+static int cv_ensure_factor(mik_handle* h) {
+  if (h->have_factor) return MIK_OK;
+  // mik_factor declares the results of an earlier predict gone (finish_factor, and mark_kids_factored when a group's exchange ends); they
+  // still lie in their landing zones, which no factor path writes, and this call promises to leave them: the flags come back
+  const int nm = (int)h->kids.size() + 1;
+  std::vector<char> had((size_t)nm);
+  for (int i = 0; i < nm; ++i) had[(size_t)i] = member(h, i)->have_results;
+  MIKC(mik_factor(h));
+  MIKC(join_exchange(h));
+  for (int i = 0; i < nm; ++i) member(h, i)->have_results = had[(size_t)i] != 0;
+  return MIK_OK;
+}
+
 int mik_cross_validate(mik_handle* h, int n_closest, double* zhat_out, double* ss_out) {
   if (!h || !zhat_out || !ss_out) return fail(MIK_EINVAL, "mik_cross_validate: NULL argument");
   if (!h->have_problem) return fail(MIK_ESTATE, "mik_cross_validate: set the problem first");
   if (n_closest != 0) return fail(MIK_EINVAL, "mik_cross_validate: only the global form (n_closest_points = 0: every other station) is built");
   if (h->pinv) return fail(MIK_EINVAL, "mik_cross_validate: the leave-one-out identity needs a regular inverse (pseudo_inv is set)");
-  if (!h->have_factor) {
-    // mik_factor declares the results of an earlier predict gone (finish_factor, and mark_kids_factored when a group's exchange ends); they
-    // still lie in their landing zones, which no factor path writes, and this call promises to leave them: the flags come back
-    const int nm = (int)h->kids.size() + 1;
-    std::vector<char> had((size_t)nm);
-    for (int i = 0; i < nm; ++i) had[(size_t)i] = member(h, i)->have_results;
-    MIKC(mik_factor(h));
-    MIKC(join_exchange(h));
-    for (int i = 0; i < nm; ++i) member(h, i)->have_results = had[(size_t)i] != 0;
-  }
+  MIKC(cv_ensure_factor(h));
   return one_cross_validate(h, zhat_out, ss_out);
+}
+
+int mik_cross_validate_folds(mik_handle* h, const int32_t* fold, int nfolds, double* zhat_out, double* ss_out) {
+  if (!h || !fold || !zhat_out || !ss_out) return fail(MIK_EINVAL, "mik_cross_validate_folds: NULL argument");
+  if (!h->have_problem) return fail(MIK_ESTATE, "mik_cross_validate_folds: set the problem first");
+  if (nfolds < 1) return fail(MIK_EINVAL, "mik_cross_validate_folds: nfolds < 1");
+  if (h->pinv) return fail(MIK_EINVAL, "mik_cross_validate_folds: the block-inverse identity needs a regular inverse (pseudo_inv is set)");
+  for (long i = 0; i < h->N; ++i)
+    if (fold[i] < 0 || fold[i] >= nfolds) return fail(MIK_EINVAL, "mik_cross_validate_folds: fold index outside [0, nfolds)");
+  MIKC(cv_ensure_factor(h));
+  return one_cross_validate_folds(h, fold, nfolds, zhat_out, ss_out);
 }
 
 int mik_statistics(mik_handle* h, double* k_out, double* ss_out) {

@@ -728,7 +728,7 @@ class _KrigingBase:
     # ---------------------------------------------------------------- leave-one-out cross-validation (mik_cross_validate)
     _CV_DOC = """Leave-one-out cross-validation on the device: every station kriged from the other stations.
 
-        ``zhat, sigmasq = obj.cross_validate(values=None, n_closest_points=None, backend="vectorized")``
+        ``zhat, sigmasq = obj.cross_validate(values=None, n_closest_points=None, backend="vectorized", folds=None)``
 
         ``values`` is ``None`` (the object's own values), ``(N,)`` or ``(N, F)`` (F fields measured at the stations, as in
         ``execute_fields``).  ``zhat`` has shape ``(N,)`` for ``None`` or 1-D values and ``(F, N)`` for 2-D values; ``sigmasq`` has
@@ -749,11 +749,49 @@ class _KrigingBase:
         checked by the backend rules of ``execute()`` (the universal-kriging classes raise as for any moving window) and the call then
         raises ``NotImplementedError``; nothing else is computed in its place.
 
+        Groups (``folds``, a keyword after the three above; ``None`` is the leave-one-out form described so far).  ``folds=K``, an
+        integer with ``2 <= K <= N``, makes K contiguous folds in the order the stations were given in, the first ``N % K`` of
+        ``N // K + 1`` stations and the rest of ``N // K`` (scikit-learn's ``KFold(K)`` without shuffle).  ``folds=labels``, an integer
+        array of shape ``(N,)`` with at least two distinct values, holds out together the stations that carry the same label
+        (leave-group-out: spatial blocks, transects, campaigns); the label values themselves do not matter.  For a fold ``S`` and
+        ``R`` = everything else (drift and border rows included) the block inverse gives
+        ``B_SS^-1 = A_SS - A_SR A_RR^-1 A_RS`` and hence ``zhat_S = v_S - B_SS^-1 c_S`` and ``sigmasq_S = diag(B_SS^-1)``, exactly:
+        every fold costs a Cholesky factorisation of its own ``|S| x |S|`` block of the one resident inverse, never another
+        factorisation of the kriging matrix.  ``folds=N`` is leave-one-out by this route (within rounding of ``folds=None``, not
+        the same bits).  Every fold leaves at least one station; whether the remainder still determines the drift terms is the
+        caller's business: a remainder too small or too degenerate for them makes ``B_SS`` ill-conditioned, like a near-zero
+        ``B_ii``.  A fold whose block is not numerically positive definite (a non-positive or non-finite pivot) returns NaN in
+        ``zhat`` and ``sigmasq`` for its stations; the other folds are unaffected and nothing is raised.  A ``folds`` that is not
+        of integer type, has the wrong shape, a ``K`` out of range or fewer than two distinct labels raises ``ValueError``.
+
         The points and results an earlier ``execute()`` left on the device stay as they are."""
 
-    def cross_validate(self, values=None, n_closest_points=None, backend="vectorized"):
+    def _fold_labels(self, folds):
+        """folds of cross_validate -> (labels 0 .. nfolds - 1 as int32 (N,), nfolds); every error is a ValueError."""
+        n = int(np.size(self._values()))
+        if isinstance(folds, (bool, np.bool_)):
+            raise ValueError("folds must be an integer K or an integer array of N labels")
+        if isinstance(folds, (int, np.integer)):
+            k = int(folds)
+            if not 2 <= k <= n:
+                raise ValueError("folds=%d: the number of folds must lie between 2 and the number of stations (%d)" % (k, n))
+            sizes = np.full(k, n // k, dtype=np.int64)
+            sizes[:n % k] += 1
+            return np.repeat(np.arange(k, dtype=np.int32), sizes), k
+        lab = np.asarray(folds)
+        if lab.dtype.kind not in "iu":
+            raise ValueError("folds must be an integer K or an array of integer labels; got dtype %s" % lab.dtype)
+        if lab.shape != (n,):
+            raise ValueError("folds has shape %s; the object has %d stations (shape (%d,))" % (lab.shape, n, n))
+        uniq, inv = np.unique(lab, return_inverse=True)
+        if uniq.size < 2:
+            raise ValueError("folds needs at least two distinct labels: one group would leave no station to krige from")
+        return np.ascontiguousarray(inv.reshape(n), dtype=np.int32), int(uniq.size)
+
+    def cross_validate(self, values=None, n_closest_points=None, backend="vectorized", folds=None):
         self._check_backend(backend, n_closest_points)
         v = None if values is None else self._field_values(values)
+        fold = None if folds is None else self._fold_labels(folds)
         if n_closest_points is not None:
             raise NotImplementedError("cross_validate: the windowed form (n_closest_points) is not built; n_closest_points=None kriges "
                                       "every station from all other stations")
@@ -764,7 +802,7 @@ class _KrigingBase:
             self._max_fields = max(self._max_fields, v.shape[1])
             h.set_fields(v.T)
         try:
-            zhat, ss = h.cross_validate(0)
+            zhat, ss = h.cross_validate(0) if fold is None else h.cross_validate_folds(*fold)
         finally:
             if v is not None:
                 h.set_fields(None)
