@@ -365,6 +365,28 @@ int  mik_set_fields(mik_handle *h, const double *values, int64_t n, int32_t nf);
 int  mik_get_field_results(mik_handle *h, double *z_out);  /* nf x npt doubles, plane f = field f, each scattered through the mask like
                                                               mik_get_results (masked points 0.0 in every plane); call it before
                                                               mik_take_results */
+
+/* Fields with missing stations (ABI 9, added without a version step like mik_cross_validate_folds: a library without the two symbols is
+ * stale).  valid is nf x n bytes, field-major like the values, 1 = measured, 0 = missing; NULL clears.  Gaps belong to the fields:
+ * mik_set_fields and mik_set_problem clear them, and the values at the missing entries are replaced by 0.0 here (whatever they were).
+ * With no gap set -- or a valid that is 1 everywhere -- every call behaves exactly as before.
+ * For a field whose stations S (m of them) are missing and R = everything else (border and drift rows included), B = A^-1, b(p) the
+ * right-hand side of point p, v0 the field with zeros at S and c0 = B[:, :n] v0 (k_cvec<8>), the block inverse gives
+ *     L L^T = B_SS,  W = L^-1 B[S, :],  g = L^-1 c0_S,  c~ = c0 - W^T g  (c~_S = 0),   z_R(p) = c~ . b(p),   sigma^2_R(p) = sigma^2(p) + |W b(p)|^2
+ * -- exactly what a problem of the stations of R alone returns (same variogram, drift terms, exact_values), for any b_S.  mik_predict groups the
+ * fields by identical valid column (a pattern without a gap does no work); per pattern one workgroup factors B[S, S] (mik_k_gaps.h on the fold
+ * kernels' device functions: m <= 96 in LDS, larger in 64-column panels), W and c~ follow from many workgroups; per launch one more
+ * fp64 MFMA GEMM W_all (rows x Mp) . Bt^T runs against the panel just written, its epilogue squares and sums per 16-row group, and a reduce adds
+ * each pattern's groups in ascending order to the launch's sigma^2.  Such a predict takes the dense path ("sparse" reads 0 in mik_timing), also on
+ * a factor in Hilbert-curve order.  Every sum has one fixed order that depends on the pattern's station list alone.  A pattern whose B_SS is not
+ * numerically positive definite gives NaN in z and sigma^2 of its fields; the others are unaffected and nothing is raised.
+ * MIK_EINVAL: gaps with pseudo_inv, on a handle that spans a device group, a field with no valid station, mik_predict_moving_window with
+ * gaps set, and a predict whose W rows (8 . rows . Mp bytes, rows = the patterns' m rounded up to 16, together to 128) would exceed a quarter
+ * of device memory.
+ * mik_get_field_sigmasq: nf x npt doubles, plane f = sigma^2 of field f (the all-stations sigma^2 for a field without gaps; fields of one
+ * pattern share their bits), scattered through the mask like mik_get_field_results; call it before mik_take_results. */
+int  mik_set_field_gaps(mik_handle *h, const uint8_t *valid /* nf x n, NULL clears */, int64_t n, int32_t nf);
+int  mik_get_field_sigmasq(mik_handle *h, double *ss_out);
 int  mik_synchronize(mik_handle *h);                       /* wait until the handle's stream is idle (every call above
                                                               already blocks; this is the explicit bracket for timing) */
 

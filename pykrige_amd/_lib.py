@@ -96,6 +96,8 @@ SIGNATURES = {
     "mik_release_results": (None, [_dp]),
     "mik_set_fields": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32]),
     "mik_get_field_results": (C.c_int, [C.c_void_p, _dp]),
+    "mik_set_field_gaps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int64, C.c_int32]),
+    "mik_get_field_sigmasq": (C.c_int, [C.c_void_p, _dp]),
     "mik_synchronize": (C.c_int, [C.c_void_p]),
     "mik_set_custom_variogram": (C.c_int, [C.c_void_p, VARIOGRAM_FN, C.c_void_p]),
     "mik_predict_moving_window": (C.c_int, [C.c_void_p, C.c_int]),
@@ -454,6 +456,20 @@ class Handle:
         z = np.empty((self._fields, self._npt), dtype=np.float64)
         check(self._lib.mik_get_field_results(self._h, _ptr(z)))
         return z
+
+    def set_field_gaps(self, valid):
+        """mik_set_field_gaps: `valid` (nf, n) booleans, one field per row like set_fields (True = measured); None clears the gaps."""
+        if valid is None:
+            check(self._lib.mik_set_field_gaps(self._h, None, 0, 0))
+            return
+        m = np.ascontiguousarray(valid, dtype=np.uint8)
+        check(self._lib.mik_set_field_gaps(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8)), int(m.shape[1]), int(m.shape[0])))
+
+    def get_field_sigmasq(self):
+        """sigma^2 of every field of the last predict, (nf, npt); before get_results, like get_field_results."""
+        ss = np.empty((self._fields, self._npt), dtype=np.float64)
+        check(self._lib.mik_get_field_sigmasq(self._h, _ptr(ss)))
+        return ss
 
     def timing(self):
         t = MikTiming()

@@ -342,6 +342,14 @@ struct mik_handle {
   PinBuf pin_fz;         // page-locked landing zone of zf (mik_get_field_results reads it, plane 0 from pin_out)
   int fv_sorted = -1;    // order of the stations in fv: 0 caller's, 1 Hilbert-curve (sort_perm), -1 not uploaded
   int nf_done = 0;       // fields the last mik_predict kriged (0: none; mik_get_field_results needs it > 0)
+  // value fields with missing stations (mik_set_field_gaps, mik_k_gaps.h): hgaps is nf x N in the caller's station order, 1 = measured;
+  // gaps_any = at least one entry is 0 (else every call behaves as without gaps).  Fields with the same column form a pattern: one
+  // block of rows in gap_W and one sigma^2 plane (gap_ss on the device, pin_gss on the host) per pattern with a gap.
+  std::vector<uint8_t> hgaps;
+  bool gaps_any = false;
+  DevBuf gap_W, gap_work, gap_list, gap_part, gap_ss;
+  PinBuf pin_gss;
+  std::vector<int> gap_plane;  // of the last mik_predict: per field its plane of pin_gss, -1 = the all-stations sigma^2 (empty: no gaps)
   // look-ahead sweep (from 3 block columns on): the next diagonal block is built and inverted ahead of the panel / update stream
   // ("early diagonal" schedule; the schedules it replaced -- rounds 1-2 -- and its flag-ordered variants left the library in round 6)
   int opt_gate = -1;       // look-ahead sweep: the trailing update waits until the next diagonal inverse has started and leaves
@@ -500,6 +508,7 @@ int sort_points(mik_handle* h, long chunk, long nchunks);                       
 int upload_fields(mik_handle* h, int want);                                                                      // mik_predict.hip
 int one_predict(mik_handle* h);                                                                                  // mik_predict.hip
 int one_predict_mw(mik_handle* h, int n_closest);
+int one_get_field_sigmasq(mik_handle* h, double* out, long ntot);                                                // mik_predict.hip
 int one_cross_validate(mik_handle* h, double* zhat_out, double* ss_out);                                         // mik_predict.hip
 int one_cross_validate_folds(mik_handle* h, const int32_t* fold, int nfolds, double* zhat_out, double* ss_out);  // mik_predict.hip
 // mik_mw_chol.hip, part N: launches class 100 G + RI of k_mw_chol if it holds it, else returns MIK_MWC_NOCLASS

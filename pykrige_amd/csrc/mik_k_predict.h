@@ -51,6 +51,7 @@ struct RhsArgs {
 }  // namespace mik
 #include "mik_k_fields.h"
 #include "mik_k_cvfolds.h"
+#include "mik_k_gaps.h"
 namespace mik {
 
 // F8 (SP only): flags per 8 stations (row stride nKf) instead of per 16.  FC > 0: no right-hand sides -- the z of FC more fields from

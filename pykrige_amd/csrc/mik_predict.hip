@@ -240,6 +240,10 @@ struct Plan {
   int Mp, nIblk, nK16, nKt, kend, nf;
   bool sparse, gathered, sortpts, lanes2;
   const unsigned* perm;  // the points of every launch in Hilbert-curve order: ps_idx[0] (else nullptr)
+  // fields with missing stations (gaps_setup): patterns with a gap, 128-row blocks of W_all, the patterns' descriptors on the device
+  bool gaps;
+  int gap_np, gap_nRblk;
+  const long* gap_desc;
 };
 
 // launch c of a plan: points [t0, t0 + nvalid), padded to palloc = 128 nTb
@@ -262,10 +266,14 @@ static int plan_predict(mik_handle* h, Plan& p) {
     HIPC(hipEventSynchronize(h->ev_d2h));
     MIKC(h->pin_fz.ensure(sizeof(double) * (size_t)(nf - 1) * (size_t)npt));
   }
+  if (nf > 0 && h->gaps_any) HIPC(hipEventSynchronize(h->ev_d2h));  // (pin_gss likewise: gaps_setup sizes it)
   long chunk = std::min<long>(h->opt_chunk, ((npt + 127) / 128) * 128);
   if (h->model == MIK_MODEL_CUSTOM) chunk = std::min<long>(chunk, 16384);  // each chunk's distances visit the host
   // range-aware contraction (k_contract_sp): the factor is in Hilbert-curve station order and the variogram has compact support
-  p.sparse = h->factor_sorted && h->opt_sparse != 2 && h->opt_sparse != 0;
+  // fields with missing stations (mik_set_field_gaps) take the dense path: W b needs the whole right-hand side, and the range-aware panel
+  // holds only the candidate tiles (a Hilbert-ordered factor is fine: the dense path accepts it)
+  p.gaps = nf > 0 && h->gaps_any;
+  p.sparse = h->factor_sorted && h->opt_sparse != 2 && h->opt_sparse != 0 && !p.gaps;
   if (p.sparse) chunk = std::min<long>(chunk, 131072);  // k_sp_tiles: at most 1024 point blocks per launch
   // tiles of gathered 16-row groups (k_contract_spg) wherever 32-bit LDS-DMA offsets reach every row of the inverse
   p.gathered = p.sparse && h->opt_sparse_rows != 128 && (double)Mp * (double)Mp * 8.0 < 4294967296.0;
@@ -448,6 +456,178 @@ static int contract_dense(mik_handle* h, const Plan& p, const Launch& l) {
   HIPC(hipEventRecord(ev.contract_end, sc));
   hipLaunchKernelGGL(k_ss_reduce, dim3((l.nvalid + 255) / 256), dim3(256), 0, sc, (const double*)pp, l.palloc, nIblk, l.nvalid,
                      h->ss.as<double>() + l.t0);
+  if (p.gaps) {  // Q = W_all Bt^T against the panel this launch has just written, squared and summed per 16-row group; then the patterns' planes
+    HIPC(hipMemsetAsync(ln.queue.p, 0, 8 * sizeof(unsigned long long), sc));
+    GapGemmArgs g{};
+    g.W = h->gap_W.as<double>(), g.ldw = ldm, g.Bt = Bi, g.ldb = ldm, g.part = h->gap_part.as<double>();
+    g.palloc = l.palloc, g.nRblk = p.gap_nRblk, g.kend = kend, g.queue = qp;
+    const unsigned ggrid = (unsigned)std::min<long>(2L * h->n_cu, super_grid(p.gap_nRblk, l.nTb));
+    hipLaunchKernelGGL((k_ss_reduce<2>), dim3(ggrid), dim3(512), 0, sc, g);
+    GapRedArgs r{};
+    r.part = g.part, r.palloc = l.palloc, r.nvalid = l.nvalid, r.ss = h->ss.as<double>() + l.t0, r.desc = p.gap_desc;
+    r.out = h->gap_ss.as<double>() + l.t0, r.ldo = p.npt;
+    hipLaunchKernelGGL(k_ss_reduce, dim3((l.nvalid + 255) / 256, p.gap_np), dim3(256), 0, sc, r);
+  }
+  return MIK_OK;
+}
+
+// Set-up of a predict whose fields have missing stations (mik_k_gaps.h), on the handle's stream behind fields_coefficients: the fields
+// are grouped by identical valid column; every pattern with a gap gets its station list in the FACTOR's order, ascending (as
+// one_cross_validate_folds builds the folds'), L^-1 of its block of the inverse, its rows of W_all and a sigma^2 plane; every field of
+// such a pattern gets c~ in its column of fc.  A pattern without a gap does no work.
+static int gaps_setup(mik_handle* h, Plan& p) {
+  const long N = h->N;
+  const int nf = h->nf, Mp = h->Mp;
+  const bool sorted = h->factor_sorted;
+  if (h->pinv) return fail(MIK_EINVAL, "mik_predict: fields with gaps need a regular inverse (pseudo_inv is set)");
+  if (h->is_kid || !h->kids.empty()) return fail(MIK_EINVAL, "mik_predict: fields with gaps are not kriged by a device group");
+  if ((long)h->hgaps.size() != (long)nf * N) return fail(MIK_ESTATE, "mik_predict: the gaps do not belong to these fields");
+  if (sorted && (long)h->sort_perm.size() != N) return fail(MIK_ESTATE, "mik_predict: station order of the factor unknown");
+  // patterns in the order their first field comes in, then the small ones (factored in LDS) in front of the large ones
+  std::map<std::string, int> seen;
+  std::vector<int> first, fraw((size_t)nf, -1);
+  std::vector<long> msize;
+  for (int f = 0; f < nf; ++f) {
+    const uint8_t* col = h->hgaps.data() + (size_t)f * N;
+    long m = 0;
+    for (long i = 0; i < N; ++i) m += col[i] == 0;
+    if (m == 0) continue;
+    std::string key((size_t)N, '0');
+    for (long i = 0; i < N; ++i) key[(size_t)i] = col[i] ? '1' : '0';
+    auto it = seen.find(key);
+    if (it == seen.end()) {
+      it = seen.emplace(std::move(key), (int)first.size()).first;
+      first.push_back(f);
+      msize.push_back(m);
+    }
+    fraw[(size_t)f] = it->second;
+  }
+  const int np = (int)first.size();
+  std::vector<int> order, place((size_t)np);
+  for (int big = 0; big < 2; ++big)
+    for (int q = 0; q < np; ++q)
+      if ((msize[(size_t)q] > MIK_CVF_LDS) == (big == 1)) order.push_back(q);
+  std::vector<long> desc((size_t)MIK_GAP_DESC * np);
+  std::vector<int> idx, grp, fpat, fcol;
+  std::vector<unsigned char> inS((size_t)np * Mp, 0);
+  long rows = 0, gld = 1;
+  size_t ltot = 0;
+  int nsmall = 0, msmall = 0;
+  for (int q = 0; q < np; ++q) {
+    const int raw = order[(size_t)q];
+    place[(size_t)raw] = q;
+    const long m = msize[(size_t)raw];
+    const uint8_t* col = h->hgaps.data() + (size_t)first[(size_t)raw] * N;
+    desc[(size_t)MIK_GAP_DESC * q] = (long)idx.size(), desc[(size_t)MIK_GAP_DESC * q + 1] = m;
+    desc[(size_t)MIK_GAP_DESC * q + 2] = (long)ltot, desc[(size_t)MIK_GAP_DESC * q + 3] = rows;
+    for (long pos = 0; pos < N; ++pos)
+      if (!col[sorted ? h->sort_perm[(size_t)pos] : pos]) {
+        idx.push_back((int)pos);
+        inS[(size_t)q * Mp + (size_t)pos] = 1;
+      }
+    for (long g = 0; g < (m + 15) / 16; ++g) grp.push_back(q);
+    rows += ((m + 15) / 16) * 16;
+    ltot += (size_t)m * (size_t)m;
+    gld = std::max(gld, m);
+    if (m <= MIK_CVF_LDS) ++nsmall, msmall = std::max(msmall, (int)m);
+  }
+  h->gap_plane.assign((size_t)nf, -1);
+  for (int f = 0; f < nf; ++f)
+    if (fraw[(size_t)f] >= 0) {
+      h->gap_plane[(size_t)f] = place[(size_t)fraw[(size_t)f]];
+      fpat.push_back(place[(size_t)fraw[(size_t)f]]);
+      fcol.push_back(f);
+    }
+  const int nq = (int)fpat.size(), ngroups = (int)grp.size();
+  const long rowsp = ((rows + MIK_BM - 1) / MIK_BM) * MIK_BM;
+  if (ngroups > 65535) return fail(MIK_EINVAL, "mik_predict: more than 65535 16-row groups of missing stations");
+  size_t freeb = 0, totalb = 0;
+  HIPC(hipMemGetInfo(&freeb, &totalb));
+  if (sizeof(double) * (double)rowsp * (double)Mp > (double)totalb / 4.0)
+    return fail(MIK_EINVAL, "mik_predict: the rows of W for the missing stations (" + std::to_string(rowsp) + " x " + std::to_string(Mp) +
+                                " doubles) would exceed a quarter of device memory");
+  p.gap_np = np, p.gap_nRblk = (int)(rowsp / MIK_BM);
+  // one list: the descriptors (longs), then idx, grp, fpat, fcol (ints), then the S masks (bytes)
+  const size_t nint = idx.size() + grp.size() + fpat.size() + fcol.size();
+  std::vector<char> blob(sizeof(long) * desc.size() + sizeof(int) * nint + inS.size());
+  {
+    char* w = blob.data();
+    auto put = [&](const void* src, size_t bytes) {
+      if (bytes) memcpy(w, src, bytes);
+      w += bytes;
+    };
+    put(desc.data(), sizeof(long) * desc.size());
+    put(idx.data(), sizeof(int) * idx.size());
+    put(grp.data(), sizeof(int) * grp.size());
+    put(fpat.data(), sizeof(int) * fpat.size());
+    put(fcol.data(), sizeof(int) * fcol.size());
+    put(inS.data(), inS.size());
+  }
+  MIKC(h->gap_list.ensure(blob.size()));
+  MIKC(h->gap_W.ensure(sizeof(double) * (size_t)rowsp * (size_t)Mp));
+  MIKC(h->gap_work.ensure(sizeof(double) * (ltot + (size_t)nq * (size_t)gld)));
+  MIKC(h->gap_part.ensure(sizeof(double) * (size_t)(rowsp / 16) * (size_t)p.chunk));
+  MIKC(h->gap_ss.ensure(sizeof(double) * (size_t)np * (size_t)p.npt));
+  MIKC(h->pin_gss.ensure(sizeof(double) * (size_t)np * (size_t)p.npt));
+  hipStream_t st = h->stream;
+  HIPC(hipMemcpyAsync(h->gap_list.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+  GapArgs a{};
+  a.B = h->T.as<double>(), a.ldb = Mp, a.Mp = Mp;
+  a.desc = h->gap_list.as<long>();
+  a.idx = reinterpret_cast<const int*>(a.desc + desc.size());
+  a.grp = a.idx + idx.size(), a.fpat = a.grp + grp.size(), a.fcol = a.fpat + fpat.size();
+  a.inS = reinterpret_cast<const unsigned char*>(a.fcol + fcol.size());
+  a.linv = h->gap_work.as<double>(), a.g = a.linv + ltot, a.gld = gld;
+  a.W = h->gap_W.as<double>(), a.fc = h->fc.as<double>(), a.ldc = Mp, a.ldw = msmall | 1;
+  p.gap_desc = a.desc;
+  if (rowsp > 16L * ngroups)  // the rows that pad W_all to whole block tiles
+    HIPC(hipMemsetAsync(a.W + (size_t)16 * ngroups * Mp, 0, sizeof(double) * (size_t)(rowsp - 16L * ngroups) * Mp, st));
+  if (nsmall) {
+    const size_t lds = sizeof(double) * (size_t)msmall * (size_t)a.ldw;
+    void (*kf)(GapArgs) = k_cvec<0>;  // (the overload with this argument)
+    HIPC(hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_cvec<0>), dim3((unsigned)nsmall), dim3(256), lds, st, a);
+  }
+  if (np > nsmall) {
+    const size_t lds = sizeof(double) * 2 * MIK_CVF_NB * MIK_CVF_TLD;
+    GapArgs b = a;
+    b.desc += (size_t)MIK_GAP_DESC * nsmall;
+    void (*kf)(GapArgs) = k_cvec<1>;
+    HIPC(hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_cvec<1>), dim3((unsigned)(np - nsmall)), dim3(256), lds, st, b);
+  }
+  const unsigned ncb = (unsigned)((Mp + 255) / 256);
+  hipLaunchKernelGGL((k_cvec<2>), dim3(ncb, (unsigned)ngroups), dim3(256), 0, st, a);
+  hipLaunchKernelGGL((k_cvec<3>), dim3((unsigned)nq), dim3(256), 0, st, a);
+  hipLaunchKernelGGL((k_cvec<4>), dim3(ncb, (unsigned)nq), dim3(256), 0, st, a);
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(st));  // blob is a local
+  return MIK_OK;
+}
+
+// sigma^2 of every field of the last predict from the landing zones, scattered through the mask like one_get_field_results: the plane of
+// the field's pattern, or the all-stations sigma^2 for a field without gaps
+int one_get_field_sigmasq(mik_handle* h, double* out, long ntot) {
+  HIPC(hipSetDevice(h->device));
+  HIPC(hipEventSynchronize(h->ev_d2h));
+  const long n = h->npt;
+  if (n == 0) return MIK_OK;
+  for (int f = 0; f < h->nf_done; ++f) {
+    const int pl = f < (int)h->gap_plane.size() ? h->gap_plane[(size_t)f] : -1;
+    const double* src = pl < 0 ? h->pin_out.as<double>() + n : h->pin_gss.as<double>() + (size_t)pl * n;
+    double* dst = out + (size_t)f * ntot;
+    if (h->scatter32 || !h->scatter.empty()) {
+      parallel_chunks(n, [&](int, long b, long e) {
+        if (h->scatter32) {
+          for (long i = b; i < e; ++i) dst[h->scatter32[i]] = src[i];
+        } else {
+          for (long i = b; i < e; ++i) dst[h->scatter[(size_t)i]] = src[i];
+        }
+      });
+    } else {
+      host_copy(dst + h->out_off, src, sizeof(double) * n);
+    }
+  }
   return MIK_OK;
 }
 
@@ -569,6 +749,9 @@ static int copy_out(mik_handle* h, const Plan& p, const Launch& l, hipStream_t s
   for (int f = 1; f < p.nf; ++f)
     HIPC(hipMemcpyAsync(h->pin_fz.as<double>() + (size_t)(f - 1) * p.npt + l.t0, h->zf.as<double>() + (size_t)(f - 1) * p.npt + l.t0, bytes,
                         hipMemcpyDeviceToHost, h->stream_d2h));
+  for (int q = 0; q < (p.gaps ? p.gap_np : 0); ++q)
+    HIPC(hipMemcpyAsync(h->pin_gss.as<double>() + (size_t)q * p.npt + l.t0, h->gap_ss.as<double>() + (size_t)q * p.npt + l.t0, bytes,
+                        hipMemcpyDeviceToHost, h->stream_d2h));
   return MIK_OK;
 }
 
@@ -637,6 +820,7 @@ int one_predict(mik_handle* h) {
   h->tm.engine = 0;  // (the v_fma_f64 contraction left the library in round 6: tools/kernel_bench)
   h->tm.mw_kernel = 0;
   h->nf_done = h->nf;
+  h->gap_plane.clear();
   if (h->npt == 0) {
     h->have_results = true;
     return MIK_OK;
@@ -648,6 +832,7 @@ int one_predict(mik_handle* h) {
   // C of the fields first: the second lane starts at ev_predict0, and every k_rhs reads C
   if (p.nf > 0) MIKC(fields_coefficients(h));
   HIPC(hipEventRecord(h->ev_predict0, h->stream));
+  if (p.gaps) MIKC(gaps_setup(h, p));
   bool sorted_now = false;
   if (p.sortpts && !(h->ps_valid && h->ps_chunk == p.chunk)) {
     MIKC(sort_points(h, p.chunk, p.nchunks));

@@ -112,13 +112,14 @@ static void destroy_one(mik_handle* h) {
                     &h->Cold2, &h->Cnew2, &h->Rt2, &h->Dinv2, &h->DinvT2, &h->Dinv3, &h->DinvT3, &h->Dnext, &h->Dcopy, &h->Rb, &h->grid.gx, &h->grid.gy, &h->grid.gz, &h->grid.orig,
                     &h->grid.cstart,
                     &h->px, &h->py, &h->pz, &h->grid_axes, &h->grid_idx, &h->Averify, &h->vbuf, &h->extra_rows, &h->z, &h->ss, &h->mw_idx, &h->mw_dist, &h->stat_S, &h->stat_x, &h->stat_out,
-                    &h->xs_s, &h->ys_s, &h->zs_s, &h->vals_s, &h->extra_cols_s, &h->sbox, &h->sp_stats, &h->dsc, &h->ps_key[0], &h->ps_key[1], &h->ps_idx[0], &h->ps_idx[1], &h->ps_table, &h->ps_box, &h->ps_x, &h->ps_y, &h->ps_z, &h->ps_zs, &h->ps_sss, &h->xpack, &h->fv, &h->fc, &h->zf};
+                    &h->xs_s, &h->ys_s, &h->zs_s, &h->vals_s, &h->extra_cols_s, &h->sbox, &h->sp_stats, &h->dsc, &h->ps_key[0], &h->ps_key[1], &h->ps_idx[0], &h->ps_idx[1], &h->ps_table, &h->ps_box, &h->ps_x, &h->ps_y, &h->ps_z, &h->ps_zs, &h->ps_sss, &h->xpack, &h->fv, &h->fc, &h->zf, &h->gap_W, &h->gap_work, &h->gap_list, &h->gap_part, &h->gap_ss};
   for (DevBuf* b : bufs) b->release();
   for (PredictLane& L : h->lane)
     for (DevBuf* b : {&L.cand, &L.flags, &L.klist, &L.kcount, &L.nrows, &L.rows, &L.rstart, &L.tiles, &L.xoff, &L.recs, &L.part, &L.queue, &L.Bt}) b->release();
   h->pin_in.release();
   h->pin_out.release();
   h->pin_fz.release();
+  h->pin_gss.release();
   for (hipEvent_t e : h->evpool) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->la_events) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ps_events) (void)hipEventDestroy(e);
@@ -580,6 +581,8 @@ static int one_set_problem(mik_handle* h, const mik_problem* p) {
   h->nf = 0;  // value fields belong to a station set (mik_set_fields)
   h->hfields.clear();
   h->fv_sorted = -1;
+  h->hgaps.clear();
+  h->gaps_any = false;
   h->have_problem = true;
   h->have_factor = false;
   h->t_state = 0;
@@ -1575,6 +1578,7 @@ int mik_predict(mik_handle* h) {
 
 int mik_predict_moving_window(mik_handle* h, int n_closest) {
   if (!h) return fail(MIK_ESTATE, "mik_predict_moving_window: NULL handle");
+  if (h->gaps_any) return fail(MIK_EINVAL, "mik_predict_moving_window: fields with gaps (mik_set_field_gaps) are kriged by mik_predict only");
   for (int i = 0; i <= (int)h->kids.size(); ++i) member(h, i)->nf_done = 0;
   MIKC(join_exchange(h));
   return for_each_device(h, [n_closest](int, mik_handle* d) { return one_predict_mw(d, n_closest); });
@@ -1805,8 +1809,53 @@ int mik_set_fields(mik_handle* h, const double* values, int64_t n, int32_t nf) {
     if (nf > 0) d->hfields.assign(values, values + (size_t)nf * (size_t)n);
     else d->hfields.clear();
     d->fv_sorted = -1;
+    d->hgaps.clear();  // gaps belong to the fields
+    d->gaps_any = false;
   }
   return MIK_OK;
+}
+
+int mik_set_field_gaps(mik_handle* h, const uint8_t* valid, int64_t n, int32_t nf) {
+  if (!h) return fail(MIK_EINVAL, "mik_set_field_gaps: NULL handle");
+  if (!valid) {
+    h->hgaps.clear();
+    h->gaps_any = false;
+    return MIK_OK;
+  }
+  if (!h->kids.empty()) return fail(MIK_EINVAL, "mik_set_field_gaps: not for a handle that spans a device group");
+  if (h->nf <= 0) return fail(MIK_ESTATE, "mik_set_field_gaps: set the fields first (mik_set_fields)");
+  if (n != h->N || nf != h->nf)
+    return fail(MIK_EINVAL, "mik_set_field_gaps: valid is " + std::to_string(nf) + " x " + std::to_string((long long)n) + ", the fields are " +
+                                std::to_string(h->nf) + " x " + std::to_string(h->N));
+  if (h->pinv) return fail(MIK_EINVAL, "mik_set_field_gaps: the block-inverse identity needs a regular inverse (pseudo_inv is set)");
+  bool any = false;
+  for (int f = 0; f < nf; ++f) {
+    long have = 0;
+    for (long i = 0; i < (long)n; ++i) have += valid[(size_t)f * n + i] != 0;
+    if (have == 0) return fail(MIK_EINVAL, "mik_set_field_gaps: field " + std::to_string(f) + " has no valid station");
+    any = any || have < (long)n;
+  }
+  h->hgaps.assign(valid, valid + (size_t)nf * (size_t)n);
+  h->gaps_any = any;
+  if (any) {  // v0: zeros at the missing stations, whatever the caller left there
+    for (size_t i = 0; i < h->hgaps.size(); ++i)
+      if (!h->hgaps[i]) h->hfields[i] = 0.0;
+    h->fv_sorted = -1;
+  }
+  return MIK_OK;
+}
+
+int mik_get_field_sigmasq(mik_handle* h, double* ss_out) {
+  if (!h || !ss_out) return fail(MIK_EINVAL, "mik_get_field_sigmasq: NULL argument");
+  if (h->nf_done <= 0) return fail(MIK_ESTATE, "mik_get_field_sigmasq: the last predict kriged no fields (mik_set_fields)");
+  if (!h->have_results) return fail(MIK_ESTATE, "mik_get_field_sigmasq: predict first (and before mik_take_results)");
+  if (!h->kids.empty()) return fail(MIK_EINVAL, "mik_get_field_sigmasq: not for a handle that spans a device group");
+  const long ntot = h->npt_total;
+  const size_t all = (size_t)h->nf_done * (size_t)ntot;
+  if (h->masked) {  // masked points keep 0.0 in every plane
+    parallel_chunks((long)all, [&](int, long b, long e) { memset(ss_out + b, 0, sizeof(double) * (size_t)(e - b)); });
+  }
+  return one_get_field_sigmasq(h, ss_out, ntot);
 }
 
 // z of every field of one device's slab, from its page-locked landing zones (filled chunk by chunk while mik_predict ran: plane 0 in

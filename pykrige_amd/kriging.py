@@ -663,9 +663,42 @@ class _KrigingBase:
         their ``execute()``: ``zvalues[f]`` is then bit for bit ``execute(..., n_closest_points=k)`` of such a per-field object, and
         ``sigmasq`` that of this object.  A point's local system does not depend on the values: the neighbour search, the local
         right-hand sides and, for windows up to 256, the factorisation of each local system are shared by up to G - 2 fields per pass
-        (G = 4, 8, 16 or 32 with the window).  The universal-kriging classes have no moving window, as in their ``execute()``."""
+        (G = 4, 8, 16 or 32 with the window).  The universal-kriging classes have no moving window, as in their ``execute()``.
 
-    def _field_values(self, values):
+        Missing stations (``valid``, the last keyword; ``None`` is everything described so far, non-finite values included: they
+        raise).  ``valid`` is a boolean array of the shape of ``values`` -- ``(N, F)``, or ``(N,)`` for 1-D values -- and True means
+        "measured".  Entries of ``values`` where ``valid`` is False are ignored (they may be NaN or inf and are replaced by 0.0 on the
+        host); entries where it is True must be finite, and every field needs at least one valid station.  The call then returns
+        ``(zvalues, sigmasq)`` with ``sigmasq`` of shape ``(F,) + shape`` under the type rules of ``zvalues``: ``zvalues[f]`` and
+        ``sigmasq[f]`` are ``execute()`` of an object built from the stations with ``valid[:, f]`` alone, with this object's
+        variogram parameters, drifts, anisotropy, ``exact_values``, centre and adjusted coordinates.  Nothing is factored again: for
+        the missing stations ``S`` of a field, ``R`` everything else, ``B`` the one resident inverse, ``b(p)`` the right-hand side of
+        point p, ``v0`` the field with zeros at ``S`` and ``c0 = B[:, :N] v0``,
+        ``L L^T = B_SS``, ``W = L^-1 B[S, :]``, ``g = L^-1 c0_S``, ``c~ = c0 - W^T g`` (``c~_S = 0``) give
+        ``z_R(p) = c~ . b(p)`` and ``sigma^2_R(p) = sigma^2(p) + |W b(p)|^2`` exactly.  Fields with the same ``valid`` column share
+        the work and the bits of their ``sigmasq`` plane; a field without gaps costs nothing extra.  A pattern whose ``B_SS`` is not
+        numerically positive definite returns NaN in its fields' planes and nothing is raised.  ``pseudo_inv=True`` raises
+        ``ValueError`` (the identity needs a regular inverse), ``n_closest_points`` together with ``valid`` raises
+        ``NotImplementedError``, and a handle that spans a device group raises ``ValueError``."""
+
+    def _field_gaps(self, values, v, valid):
+        """valid of execute_fields against the (N, F) values v: the (N, F) boolean array; v gets 0.0 where it is False."""
+        m = np.asarray(valid)
+        if m.dtype != np.bool_:
+            raise ValueError("valid must be a boolean array (True = measured); got dtype %s" % m.dtype)
+        want = (v.shape[0],) if np.ndim(values) == 1 else v.shape
+        if m.shape != want:
+            raise ValueError("valid has shape %s; values has shape %s" % (m.shape, want))
+        m = m.reshape(v.shape)
+        if not np.all(np.isfinite(v[m])):
+            raise ValueError("values holds non-finite entries where valid is True")
+        empty = np.flatnonzero(~m.any(axis=0))
+        if empty.size:
+            raise ValueError("valid: field %d has no valid station" % int(empty[0]))
+        v[~m] = 0.0
+        return m
+
+    def _field_values(self, values, valid=None):
         n = int(np.size(self._values()))
         v = np.array(values, copy=True, dtype=np.float64)
         if v.ndim == 1:
@@ -676,16 +709,26 @@ class _KrigingBase:
             raise ValueError("values has %d rows; the object has %d stations" % (v.shape[0], n))
         if v.shape[1] == 0:
             raise ValueError("values holds no field (F = 0)")
-        if not np.all(np.isfinite(v)):
+        if valid is None and not np.all(np.isfinite(v)):
             raise ValueError("values holds non-finite entries")
         return v
 
-    def _execute_fields(self, style, axes, values, mask, backend, prepare_kw, n_closest_points=None):
+    def _execute_fields(self, style, axes, values, mask, backend, prepare_kw, n_closest_points=None, valid=None):
         """execute_fields of the four classes: every argument is checked on the host before the device is touched."""
         if style != "grid" and style != "masked" and style != "points":
             raise ValueError("style argument must be 'grid', 'points', or 'masked'")
         self._check_backend(backend, n_closest_points)
-        v = self._field_values(values)
+        v = self._field_values(values, valid)
+        gaps = None
+        if valid is not None:
+            gaps = self._field_gaps(values, v, valid)
+            if n_closest_points is not None:
+                raise NotImplementedError("execute_fields: valid together with n_closest_points (the moving window with gaps) is not built")
+            if self.pseudo_inv:
+                raise ValueError("execute_fields with valid needs a regular inverse: the block-inverse identity does not hold for pseudo_inv=True")
+            if self._handle is not None and self._handle.n_devices > 1:
+                raise ValueError("execute_fields with valid: this object's handle spans a device group of %d devices; fields with gaps "
+                                 "are kriged on one device" % self._handle.n_devices)
         if n_closest_points is not None and int(n_closest_points) > v.shape[0]:
             raise ValueError("n_closest_points exceeds the number of stations")  # what mik_predict_moving_window answers execute()
         P = self._prepare(style, axes, mask, **prepare_kw)
@@ -699,6 +742,11 @@ class _KrigingBase:
         P.load(h, self._ndim, with_extra=n_closest_points is None)
         h.set_fields(v.T)
         try:
+            if gaps is not None:
+                if h.n_devices > 1:
+                    raise ValueError("execute_fields with valid: this object's handle spans a device group of %d devices; fields with "
+                                     "gaps are kriged on one device" % h.n_devices)
+                h.set_field_gaps(gaps.T)
             if n_closest_points is None:
                 h.predict()
             else:
@@ -710,9 +758,14 @@ class _KrigingBase:
                     raise
             self.last_timing = h.timing()
             zf = h.get_field_results()  # (before get_results: that one may take the landing zone over)
+            ssf = None if gaps is None else h.get_field_sigmasq()
             _, ss = h.get_results()
         finally:
-            h.set_fields(None)
+            h.set_fields(None)  # (clears the gaps with the fields)
+        if ssf is not None:
+            zf, _ = self._finish_fields(zf, ss, style, P.shape, P.mask, backend)
+            ssf, _ = self._finish_fields(ssf, ss, style, P.shape, P.mask, backend)
+            return zf, ssf
         return self._finish_fields(zf, ss, style, P.shape, P.mask, backend)
 
     def _finish_fields(self, zf, ss, style, shape, mask, backend):
@@ -922,8 +975,8 @@ class OrdinaryKriging(_KrigingBase):
             z, ss = self._solve(P)
         return self._finish(z, ss, style, P.shape, P.mask, backend)
 
-    def execute_fields(self, style, xpoints, ypoints, values, mask=None, backend="vectorized", n_closest_points=None):
-        return self._execute_fields(style, (xpoints, ypoints), values, mask, backend, {}, n_closest_points)
+    def execute_fields(self, style, xpoints, ypoints, values, mask=None, backend="vectorized", n_closest_points=None, valid=None):
+        return self._execute_fields(style, (xpoints, ypoints), values, mask, backend, {}, n_closest_points, valid)
 
     execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
 
@@ -1050,9 +1103,9 @@ class UniversalKriging(OrdinaryKriging):
         z, ss = self._solve(P)
         return self._finish(z, ss, style, P.shape, P.mask, backend)
 
-    def execute_fields(self, style, xpoints, ypoints, values, mask=None, backend="vectorized", specified_drift_arrays=None):
+    def execute_fields(self, style, xpoints, ypoints, values, mask=None, backend="vectorized", specified_drift_arrays=None, valid=None):
         return self._execute_fields(style, (xpoints, ypoints), values, mask, backend,
-                                    dict(specified_drift_arrays=specified_drift_arrays, backend=backend))
+                                    dict(specified_drift_arrays=specified_drift_arrays, backend=backend), valid=valid)
 
     execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
 
@@ -1166,8 +1219,8 @@ class OrdinaryKriging3D(_KrigingBase):
             z, ss = self._solve(P)
         return self._finish(z, ss, style, P.shape, P.mask, backend)
 
-    def execute_fields(self, style, xpoints, ypoints, zpoints, values, mask=None, backend="vectorized", n_closest_points=None):
-        return self._execute_fields(style, (xpoints, ypoints, zpoints), values, mask, backend, {}, n_closest_points)
+    def execute_fields(self, style, xpoints, ypoints, zpoints, values, mask=None, backend="vectorized", n_closest_points=None, valid=None):
+        return self._execute_fields(style, (xpoints, ypoints, zpoints), values, mask, backend, {}, n_closest_points, valid)
 
     execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
 
@@ -1247,9 +1300,9 @@ class UniversalKriging3D(OrdinaryKriging3D):
         z, ss = self._solve(P)
         return self._finish(z, ss, style, P.shape, P.mask, backend)
 
-    def execute_fields(self, style, xpoints, ypoints, zpoints, values, mask=None, backend="vectorized", specified_drift_arrays=None):
+    def execute_fields(self, style, xpoints, ypoints, zpoints, values, mask=None, backend="vectorized", specified_drift_arrays=None, valid=None):
         return self._execute_fields(style, (xpoints, ypoints, zpoints), values, mask, backend,
-                                    dict(specified_drift_arrays=specified_drift_arrays))
+                                    dict(specified_drift_arrays=specified_drift_arrays), valid=valid)
 
     execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
 
