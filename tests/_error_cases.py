@@ -2,9 +2,17 @@
 tests/test_exact_reference.py on the CPU): kriging problems at the shapes, magnitudes and edges where kernels go wrong, each with
 its exact answer (oracle/exact_kriging.py) cached for the session.
 
+The moving window has four per-point solvers (timing()["mw_kernel"]), and each has its own groups: `mw` puts a window on both sides
+of every LDL^T register class (1: k_mw_chol); `mw_piv` on both sides of the six Gauss-Jordan classes of dispatch_mw_solve (2:
+k_mw_solve, nb = K + 1 <= 16, 32, 48, 64, 96, 128), of the hand-off to the scratch-slot LU at K = 127 | 128 (3: k_mw_solve_big) and
+of the wrap of its 256-thread row strides at nb = 256 | 257; `mw_blocked` on the 64-wide panel edges of k_mw_chol_blocked (4:
+K = 64 | 65, 128 | 129, 320 | 321, 384 | 385), a single panel, a mostly padded last panel and the shift it reduces across its four
+wavefronts for the unbounded models.  Each solver also meets a 3-D and a geographic station set-up.  custom_problem / custom_state
+are the custom-variogram problems that only the class API can carry (a Python callable, its K x K table gtab).
+
 A case is a dict: group, name, st (KrigingState whose coords_adj are what the device is given), pts (adjusted points), k (moving
-window size or None), opts (library options), sparse (expected value of timing()["sparse"], or None) and, for the golden fixtures,
-golden / sel (the fixture name and the grid cells compared)."""
+window size or None), opts (library options), sparse (expected value of timing()["sparse"], or None), mw_kernel (expected value of
+timing()["mw_kernel"], or absent) and, for the golden fixtures, golden / sel (the fixture name and the grid cells compared)."""
 import functools
 
 import numpy as np
@@ -134,7 +142,8 @@ def _sparse_cases():
     return out
 
 
-# dispatch_mw_chol's class limits, MIK_MW_KMAX = 127 (registers -> HBM) and 256 / 257 (k_mw_chol_blocked)
+# mw_chol_class's limits (mik_mw.hip: the {G, RI} register classes of k_mw_chol), 127 | 128 inside class {16, 8} and the hand-off to
+# k_mw_chol_blocked at MIK_MW_CHOL_KMAX = 256 | 257
 MW_LIMITS = [16, 24, 32, 40, 48, 52, 64, 80, 88, 96, 104, 112, 128, 144, 160, 176, 192, 208, 224, 256]
 MW_KS = sorted(set([k for L in MW_LIMITS for k in (L, L + 1)] + [127]))
 
@@ -156,7 +165,7 @@ def _mw_cases():
         p = rng.random((6, 2))
         st = _state(c, _field(c), model, USER[model])
         _no_ties(st, p, k)
-        out.append(dict(group="mw", name="k%d_%s" % (k, model), st=st, pts=p, k=k, opts={}, sparse=None))
+        out.append(dict(group="mw", name="k%d_%s" % (k, model), st=st, pts=p, k=k, opts={}, sparse=None, mw_kernel=1 if k <= 256 else 4))
     rng = np.random.default_rng(399)
     c = rng.random((200, 2))
     for name, model, opts in (("hole_effect", "hole-effect", {}), ("mw_pivot", "exponential", {"mw_pivot": 1}),
@@ -167,14 +176,148 @@ def _mw_cases():
         p = rng.random((12, 2)) * (cc.max(0) - cc.min(0)) + cc.min(0)
         st = _state(cc, _field(c), model, user)
         _no_ties(st, p, 30)
-        out.append(dict(group="mw", name=name, st=st, pts=p, k=30, opts=opts, sparse=None))
+        out.append(dict(group="mw", name=name, st=st, pts=p, k=30, opts=opts, sparse=None, mw_kernel=1 if name.endswith("utm") else 2))
     lon, lat = rng.uniform(-180, 180, 300), rng.uniform(-85, 85, 300)
     st = _state(np.stack([lon, lat], 1), np.cos(np.radians(lat)) * np.sin(np.radians(2 * lon)), "exponential", [1.0, 40.0, 0.02],
                 geographic=True)
     p = np.stack([np.concatenate([rng.uniform(175, 180, 4), rng.uniform(-180, -175, 4)]), rng.uniform(-80, 80, 8)], 1)
     _no_ties(st, p, 20)
-    out.append(dict(group="mw", name="geographic", st=st, pts=p, k=20, opts={}, sparse=None))
+    out.append(dict(group="mw", name="geographic", st=st, pts=p, k=20, opts={}, sparse=None, mw_kernel=1))
     return out
+
+
+# dispatch_mw_solve's class limits are nb = K + 1 <= 16, 32, 48, 64, 96, 128 (k_mw_solve, mw_kernel 2); from K = 128 = MIK_MW_KMAX + 1
+# the system lives in a scratch slot (k_mw_solve_big, mw_kernel 3), whose 256-thread strides over nb rows wrap at nb = 256 | 257
+PIV_KS = [2, 15, 16, 31, 32, 47, 48, 63, 64, 95, 96, 127, 128, 129, 255, 256, 257]
+HOLE_GEOGRAPHIC = [1.0, 40.0, 0.05]  # hole-effect parameters on the sphere (range in degrees)
+
+
+def _piv_kernel(k):
+    return 2 if k <= 127 else 3
+
+
+def _piv_points(rng, c, draw, k):
+    """19 points for k_mw_solve (its smallest class packs 16 per block: one full block and a partial one), 6 for k_mw_solve_big; the first
+    two coincide with stations (the exact-hit rule through the pivoting solvers)."""
+    p = draw(19 if _piv_kernel(k) == 2 else 6)
+    p[:2] = c[rng.choice(c.shape[0], 2, replace=False)]
+    return p
+
+
+def _aniso3(rng, n):
+    """3-D stations with anisotropy-adjusted coordinates as _dense_cases builds them: (original, adjusted, the adjustment)."""
+    c0 = rng.random((n, 3))
+    adj = lambda x: ko.adjust_for_anisotropy(x, c0.mean(0), [1.5, 0.7], [20.0, 10.0, 30.0])  # noqa: E731
+    return c0, adj(c0), adj
+
+
+def _globe(rng, n):
+    """Stations all over the sphere as mw/geographic has them: (lon / lat columns, values)."""
+    lon, lat = rng.uniform(-180, 180, n), rng.uniform(-85, 85, n)
+    return np.stack([lon, lat], 1), np.cos(np.radians(lat)) * np.sin(np.radians(2 * lon))
+
+
+def _across_antimeridian(rng, npt):
+    h = npt // 2
+    return np.stack([np.concatenate([rng.uniform(175, 180, h), rng.uniform(-180, -175, npt - h)]), rng.uniform(-80, 80, npt)], 1)
+
+
+def _mw_piv_cases():
+    out = []
+
+    def add(name, st, p, k, opts=None):
+        _no_ties(st, p, k)
+        out.append(dict(group="mw_piv", name=name, st=st, pts=p, k=k, opts=opts or {}, sparse=None, mw_kernel=_piv_kernel(k)))
+
+    for k in PIV_KS:  # hole-effect: no positive definite station block, hence pivoting by default
+        rng = np.random.default_rng(600 + k)
+        c = rng.random((300, 2))
+        add("hole_k%d" % k, _state(c, _field(c), "hole-effect", USER["hole-effect"]), _piv_points(rng, c, lambda m: rng.random((m, 2)), k), k)
+    for k in (16, 64, 128):
+        rng = np.random.default_rng(900 + k)
+        c0, c, adj = _aniso3(rng, 300)
+        add("hole_3d_k%d" % k, _state(c, _field(c0), "hole-effect", USER["hole-effect"]),
+            _piv_points(rng, c, lambda m: adj(rng.random((m, 3))), k), k)
+    for k in (40, 130):
+        rng = np.random.default_rng(1100 + k)
+        c, v = _globe(rng, 300)
+        add("hole_geographic_k%d" % k, _state(c, v, "hole-effect", HOLE_GEOGRAPHIC, geographic=True),
+            _piv_points(rng, c, lambda m: _across_antimeridian(rng, m), k), k)
+    for model, k in (("linear", 48), ("linear", 49), ("power", 128)):  # "mw_pivot": the unshifted systems of the unbounded models
+        rng = np.random.default_rng(1300 + k)
+        c = rng.random((300, 2))
+        add("pivot_%s_k%d" % (model, k), _state(c, _field(c), model, USER[model]), _piv_points(rng, c, lambda m: rng.random((m, 2)), k), k,
+            {"mw_pivot": 1})
+    rng = np.random.default_rng(1500)
+    u = rng.random((300, 2))
+    c = u * 1e4 + np.array([5e5, 4.1e6])  # mw/linear_utm's offset and extent
+    add("pivot_linear_utm_k96", _state(c, _field(u), "linear", [USER["linear"][0] * 1e-4] + USER["linear"][1:]),
+        _piv_points(rng, c, lambda m: rng.random((m, 2)) * 1e4 + np.array([5e5, 4.1e6]), 96), 96, {"mw_pivot": 1})
+    return out
+
+
+# k_mw_chol_blocked (mw_kernel 4) pads the system to ldc = 64 ceil(K / 64): panel edges at K = 320 | 321 and 384 | 385 by default
+# (K > 256); "mw_class" 1 sends smaller windows to it: the smallest it takes (8), a single panel (63, 64), a last panel of one real
+# row (65, 129) and a full second one (128)
+def _mw_blocked_cases():
+    out = []
+    bounded = ["exponential", "spherical", "gaussian"]
+
+    def add(name, st, p, k, opts=None):
+        _no_ties(st, p, k)
+        out.append(dict(group="mw_blocked", name=name, st=st, pts=p, k=k, opts=opts or {}, sparse=None, mw_kernel=4))
+
+    for i, (k, n, opts) in enumerate([(k, 450, {}) for k in (320, 321, 384, 385)] + [(k, 300, {"mw_class": 1}) for k in (8, 63, 64, 65, 128, 129)]):
+        model = bounded[i % 3]
+        rng = np.random.default_rng(1700 + k)
+        c = rng.random((n, 2))
+        add("%sk%d_%s" % ("class1_" if opts else "", k, model), _state(c, _field(c), model, USER[model]), rng.random((6, 2)), k, opts)
+    for model in ("linear", "power"):  # no sill: the shift is 4 max gamma of the window, reduced across the four wavefronts
+        rng = np.random.default_rng(1900 + len(model))
+        c = rng.random((450, 2))
+        add("k270_%s" % model, _state(c, _field(c), model, USER[model]), rng.random((6, 2)), 270)
+    rng = np.random.default_rng(2100)
+    c0, c, adj = _aniso3(rng, 450)
+    add("k270_3d_spherical", _state(c, _field(c0), "spherical", USER["spherical"]), adj(rng.random((6, 3))), 270)
+    rng = np.random.default_rng(2101)
+    c, v = _globe(rng, 450)
+    add("k270_geographic_exponential", _state(c, v, "exponential", [1.0, 40.0, 0.02], geographic=True), _across_antimeridian(rng, 6), 270)
+    return out
+
+
+# Custom variograms reach the device through the class API alone (a Python callable evaluated on the host; the K x K table gtab of a
+# point's station pairs enters k_mw_solve and k_mw_solve_big): window size -> the solver it exercises
+CUSTOM_KS = {31: 2, 32: 2, 130: 3}
+
+
+def custom_exponential(p, d):
+    """The reference's exponential model written out.  A custom model's parameter list is used as it is given (no sill - nugget)."""
+    return p[0] * (1 - np.exp(-d / (p[1] / 3))) + p[2]
+
+
+@functools.lru_cache(maxsize=None)
+def custom_problem(k):
+    """(stations, values, points) of the custom-variogram case at window k, as the user hands them to OrdinaryKriging; two of the
+    points coincide with stations."""
+    rng = np.random.default_rng(2300 + k)
+    c = rng.random((300, 2))
+    p = rng.random((19 if CUSTOM_KS[k] == 2 else 6, 2))
+    p[:2] = c[rng.choice(300, 2, replace=False)]
+    return c, _field(c), p
+
+
+def custom_state(k, xa=None, ya=None):
+    """The custom case at window k as a case of the NAMED exponential model with the callable's parameters, on the kriging object's
+    adjusted station coordinates xa, ya (default: the oracle's own adjustment about the same centre), and the points adjusted the same way."""
+    c, v, p = custom_problem(k)
+    center = (c.max(0) + c.min(0)) / 2.0  # ok.py:276-277
+    ca = ko.adjust_for_anisotropy(c, center, [1.0], [0.0]) if xa is None else np.stack([xa, ya], 1)
+    st = _state(ca, v, "exponential", USER["exponential"])
+    st.params = [float(x) for x in USER["exponential"]]
+    pa = ko.adjust_for_anisotropy(p, center, [1.0], [0.0])
+    _no_ties(st, pa, k)
+    return dict(group="custom", name="exponential_k%d%s" % (k, "" if xa is None else "_object"), st=st, pts=pa, k=k, opts={}, sparse=None,
+                mw_kernel=CUSTOM_KS[k])
 
 
 HIT_DISTANCES = [0.0, 1e-12, 5e-11, 2e-10, 1e-8]  # none within a few ulps of EPS = 1e-10
@@ -225,7 +368,8 @@ def _golden_cases():
 
 @functools.lru_cache(maxsize=None)
 def cases():
-    return tuple(_dense_cases() + _magnitude_cases() + _sparse_cases() + _mw_cases() + _exact_hit_cases() + _golden_cases())
+    return tuple(_dense_cases() + _magnitude_cases() + _sparse_cases() + _mw_cases() + _mw_piv_cases() + _mw_blocked_cases() +
+                 _exact_hit_cases() + _golden_cases())
 
 
 def case(name):

@@ -129,6 +129,18 @@ def test_float64_oracle_meets_the_bar(cid):
     assert rz <= 1.0 and rs <= 1.0, (cid, rz, rs)
 
 
+@pytest.mark.parametrize("k", sorted(ec.CUSTOM_KS))
+def test_float64_oracle_meets_the_bar_on_the_custom_variogram_cases(k):
+    """The CPU twin of test_custom_variogram_within_the_extended_precision_bar: the float64 oracle on the named exponential model
+    meets the bar on the state the device's custom callable is held to -- and that callable is the named model, to rounding."""
+    c = ec.custom_state(k)
+    z, ss = ec.oracle(c)
+    rz, rs, _, _ = ec.ratios(c, z, ss)
+    assert rz <= 1.0 and rs <= 1.0, (k, rz, rs)
+    d = np.linspace(0.0, 1.5, 301)
+    assert np.allclose(ec.custom_exponential(ec.USER["exponential"], d), ko.variogram("exponential", c["st"].params, d), rtol=1e-15, atol=0)
+
+
 def test_every_execute_fixture_is_in_the_matrix():
     have = {c["golden"] for c in ec.cases() if c["group"] == "golden"}
     assert have == {n for n in fx.names() if "z" in fx.load(n)}

@@ -10,9 +10,13 @@ spherical range dropped by k_sp_cand, a gamma off by 1e-9 relative in k_rhs) fai
 
 The case matrix (tests/_error_cases.py): the dense path across the 16- and 128-wide tiles, launch chunks and the factor /
 symmetric / tri options; values, sills and coordinates far from order 1 through the dense, range-aware and moving-window paths;
-stations just inside the spherical range, points with none, geographic problems across the antimeridian and at the poles; moving
-windows on both sides of every dispatch_mw_chol limit, MIK_MW_KMAX and the blocked solve; the exact-hit rule; every execute fixture
-of tests/golden.  The CPU side (tests/test_exact_reference.py) checks the exact reference against mpmath and shows that the float64
+stations just inside the spherical range, points with none, geographic problems across the antimeridian and at the poles; the
+moving window's four solvers, each asserted through timing()["mw_kernel"] -- windows on both sides of every LDL^T class of
+mw_chol_class (k_mw_chol); of the six pivoting classes of dispatch_mw_solve (k_mw_solve: nb = K + 1 <= 16, 32, 48, 64, 96, 128), of
+its hand-off to k_mw_solve_big at K = 127 | 128 and of that kernel's 256-thread row strides at nb = 256 | 257; on the 64-wide panel
+edges of k_mw_chol_blocked (K = 64 | 65, 128 | 129, 320 | 321, 384 | 385), with a single panel, a mostly padded last panel and the
+shift of the unbounded models; 3-D and geographic station set-ups through each; custom variograms (the K x K table gtab) through
+the class API into both pivoting solvers; the exact-hit rule; every execute fixture of tests/golden.  The CPU side (tests/test_exact_reference.py) checks the exact reference against mpmath and shows that the float64
 oracle meets the same bar on every case."""
 import collections
 
@@ -71,7 +75,11 @@ def _check(c, z, ss):
 @pytest.mark.parametrize("cid", ec.ids())
 def test_device_within_the_extended_precision_bar(cid):
     """Regression notes: no case has failed on the device.  First MI355X run at C = 8: worst err / bar 0.52 (sigma^2, dense linear
-    model, N = 257, one point, chunk 128), i.e. an error of 4.1 u (cond_1 + M) max|b|; every other group below 0.4."""
+    model, N = 257, one point, chunk 128), i.e. an error of 4.1 u (cond_1 + M) max|b|; every other group below 0.4.
+    First run of the groups of the pivoting and blocked moving-window solvers (same bar): every case ran the solver it names and none
+    was redone with pivoting; worst err / bar of mw_piv 0.077 (sigma^2; z 0.029: hole_k2, cond_1 15.7 -- the 3 x 3 system, where the
+    bar is 8 u (15.7 + 3)); of mw_blocked 0.005 (sigma^2; z 0.001: class1_k8_spherical); of the
+    custom variograms through the class API 0.001.  No kernel defect found."""
     c = ec.case(cid)
     if c["group"] == "golden":
         z, ss, t = _run_golden(c)
@@ -79,7 +87,24 @@ def test_device_within_the_extended_precision_bar(cid):
         z, ss, t = _run_handle(c)
     if c["sparse"] is not None:
         assert t["sparse"] == c["sparse"], t  # the range-aware path was (not) taken, as the case intends
+    if c.get("mw_kernel") is not None:
+        assert t["mw_kernel"] == c["mw_kernel"], t  # the solver the case is meant for (2 or 3 in place of 1 or 4: redone with pivoting)
     _check(c, z, ss)
+
+
+@pytest.mark.parametrize("k", sorted(ec.CUSTOM_KS))
+def test_custom_variogram_within_the_extended_precision_bar(k):
+    """A custom variogram -- the reference's exponential model written out as a Python callable -- through OrdinaryKriging.execute
+    with n_closest_points: its K x K table gtab enters k_mw_solve (K = 31 | 32, the nb <= 32 class limit) and k_mw_solve_big
+    (K = 130).  Held to the exact reference of the NAMED model on the object's own adjusted coordinates, same bar."""
+    import pykrige_amd as pa
+
+    c, v, p = ec.custom_problem(k)
+    m = pa.OrdinaryKriging(c[:, 0], c[:, 1], v, variogram_model="custom", variogram_parameters=list(ec.USER["exponential"]),
+                           variogram_function=ec.custom_exponential)
+    z, ss = m.execute("points", p[:, 0], p[:, 1], backend="loop", n_closest_points=k)
+    assert m.last_timing["mw_kernel"] == ec.CUSTOM_KS[k], m.last_timing
+    _check(ec.custom_state(k, m.X_ADJUSTED, m.Y_ADJUSTED), np.ma.getdata(z).ravel(), np.ma.getdata(ss).ravel())
 
 
 def test_zz_worst_ratio_per_group():
