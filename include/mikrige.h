@@ -427,6 +427,26 @@ int  mik_cross_validate(mik_handle *h, int n_closest_points /* 0 = global */, do
  * (Added without a new ABI version: no existing signature or field changed.) */
 int  mik_cross_validate_folds(mik_handle *h, const int32_t *fold /* n */, int nfolds, double *zhat_out /* nf x n */, double *ss_out /* n */);
 
+/* The kriging error covariance between the resident points (ABI 9, added without a version step: a library without the symbol is stale).
+ * With b(p) the right-hand side of point p exactly as mik_predict forms it (drift rows, the border row and the exact_values zeroing
+ * included), B = A^-1 and e_p = Z(p) - zhat(p),
+ *     cov(e_p, e_q) = -gamma*(d_pq) - b(p)^T B b(q),     gamma*(d) = 0 if d <= eps (mik_problem.eps), else the problem's variogram at d,
+ * d_pq the distance between the adjusted points (geographic: the great-circle distance of the right-hand sides) -- for ordinary and universal
+ * kriging alike; p = q is mik_predict's sigma^2, and with exact_values the rows of points that sit on a station are zero.
+ * The call needs mik_set_problem and resident points, factors if no factor is resident and runs the predict: z and sigma^2 are bit for bit
+ * mik_predict's and stay retrievable by mik_get_results / mik_take_results.  A dense predict writes the right-hand sides of its launches into one
+ * panel of all Pp = 128 ceil(npt / 128) points and contracts from there; a range-aware one ("sparse" reads 1 in mik_timing) runs as always and one
+ * more dense k_rhs pass writes that panel;
+ * then (mik_k_cov.h) an elementwise kernel writes -gamma* above the diagonal, one fp64 MFMA GEMM forms Yt = Bt B^T (Pp x Mp), a second one the
+ * upper block triangle of Bt Yt^T, whose epilogue stores every off-diagonal element to [p][q] and [q][p] (cov_out is exactly symmetric) and copies
+ * the diagonal from sigma^2.  The result does not depend on how "chunk" cuts the predict into launches.  cov_out (npt x npt doubles, row-major,
+ * the order of the resident points) is filled row block by row block through a page-locked staging buffer.
+ * cov_out = NULL runs the checks only: MIK_OK says that the same call with a buffer would pass them; nothing is launched.
+ * MIK_EINVAL, before anything is launched: a custom variogram, pseudo_inv, a handle that spans a device group, masked points, no points, fields with
+ * gaps, and buffers -- two of Pp x Mp and one of Pp x Pp doubles -- beyond a quarter of device memory (the message names the largest number of points
+ * that fits). */
+int  mik_predict_cov(mik_handle *h, double *cov_out /* npt x npt, row-major */);
+
 /* Variogram-fit statistics: replaces core._find_statistics -> core._krige (core.py:759-836, 654-756): for
  * i = 1..n-1 station i is kriged from stations 0..i-1.  k_out / ss_out have n entries (entry 0 unused = 0). */
 int  mik_statistics(mik_handle *h, double *k_out, double *ss_out);

@@ -100,6 +100,7 @@ SIGNATURES = {
     "mik_get_field_sigmasq": (C.c_int, [C.c_void_p, _dp]),
     "mik_synchronize": (C.c_int, [C.c_void_p]),
     "mik_set_custom_variogram": (C.c_int, [C.c_void_p, VARIOGRAM_FN, C.c_void_p]),
+    "mik_predict_cov": (C.c_int, [C.c_void_p, _dp]),
     "mik_predict_moving_window": (C.c_int, [C.c_void_p, C.c_int]),
     "mik_cross_validate": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "mik_cross_validate_folds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, _dp, _dp]),
@@ -362,6 +363,17 @@ class Handle:
     def predict(self):
         self._taken = None  # the previous results stay valid for whoever holds them; the handle lets go of them
         check(self._lib.mik_predict(self._h))
+
+    def predict_cov(self):
+        """mik_predict_cov: the predict of the resident points with their error covariance, cov[p, q] = -gamma*(d_pq) - b(p)^T A^-1 b(q), a
+        C-contiguous (npt, npt) float64 array in the order of the resident points.  z and sigma^2 are mik_predict's bits (get_results).  The
+        library's checks run first without a buffer (cov_out = NULL): a refusal -- ValueError -- allocates and launches nothing."""
+        self._taken = None
+        check(self._lib.mik_predict_cov(self._h, None))
+        n = int(self._npt)
+        cov = np.empty((n, n), dtype=np.float64)
+        check(self._lib.mik_predict_cov(self._h, _ptr(cov)))
+        return cov
 
     def predict_moving_window(self, n_closest_points):
         self._taken = None

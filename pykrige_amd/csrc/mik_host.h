@@ -350,6 +350,10 @@ struct mik_handle {
   DevBuf gap_W, gap_work, gap_list, gap_part, gap_ss;
   PinBuf pin_gss;
   std::vector<int> gap_plane;  // of the last mik_predict: per field its plane of pin_gss, -1 = the all-stations sigma^2 (empty: no gaps)
+  // error covariance (mik_predict_cov, mik_k_cov.h): the two page-locked pieces C leaves through; events around the stages [0..3] and
+  // behind the two pieces [4..5], created by the first call
+  PinBuf pin_cov;
+  hipEvent_t ev_cov[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   // look-ahead sweep (from 3 block columns on): the next diagonal block is built and inverted ahead of the panel / update stream
   // ("early diagonal" schedule; the schedules it replaced -- rounds 1-2 -- and its flag-ordered variants left the library in round 6)
   int opt_gate = -1;       // look-ahead sweep: the trailing update waits until the next diagonal inverse has started and leaves
@@ -507,6 +511,7 @@ int one_factor(mik_handle* h);                                                  
 int sort_points(mik_handle* h, long chunk, long nchunks);                                                        // mik_predict.hip
 int upload_fields(mik_handle* h, int want);                                                                      // mik_predict.hip
 int one_predict(mik_handle* h);                                                                                  // mik_predict.hip
+int one_predict_cov(mik_handle* h, double* cov_out);                                                             // mik_predict.hip
 int one_predict_mw(mik_handle* h, int n_closest);
 int one_get_field_sigmasq(mik_handle* h, double* out, long ntot);                                                // mik_predict.hip
 int one_cross_validate(mik_handle* h, double* zhat_out, double* ss_out);                                         // mik_predict.hip

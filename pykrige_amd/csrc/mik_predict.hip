@@ -1,6 +1,7 @@
 // mik_predict.hip -- K3: right-hand sides + dense / range-aware contraction of the resident points
 // One translation unit of libmikrige.so (pykrige_amd/build.py compiles them in parallel).
 #include "mik_k_predict.h"
+#include "mik_k_cov.h"
 #include "mik_host.h"
 
 // unit vectors of the resident (geographic) points, gu[0 .. npt) x, [npt .. 2 npt) y, [2 npt .. 3 npt) z; on the handle's stream
@@ -244,6 +245,9 @@ struct Plan {
   bool gaps;
   int gap_np, gap_nRblk;
   const long* gap_desc;
+  // a predict with the error covariance (one_predict_cov) on the dense path: every launch writes its panel into the one panel of all
+  // points, at t0 * Mp, and contracts from there (nullptr: the lane's panel)
+  double* panel;
 };
 
 // launch c of a plan: points [t0, t0 + nvalid), padded to palloc = 128 nTb
@@ -255,7 +259,7 @@ struct Launch {
 };
 
 // chunk size and count, path, lanes and point sort of this predict; the timing fields that describe them; the work buffers and events
-static int plan_predict(mik_handle* h, Plan& p) {
+static int plan_predict(mik_handle* h, Plan& p, bool cov) {
   const long npt = h->npt;
   const int Mp = h->Mp, nIblk = Mp / 128, nf = h->nf;
   p.npt = npt, p.Mp = Mp, p.nIblk = nIblk, p.nK16 = Mp / 16, p.nf = nf;
@@ -274,6 +278,9 @@ static int plan_predict(mik_handle* h, Plan& p) {
   // holds only the candidate tiles (a Hilbert-ordered factor is fine: the dense path accepts it)
   p.gaps = nf > 0 && h->gaps_any;
   p.sparse = h->factor_sorted && h->opt_sparse != 2 && h->opt_sparse != 0 && !p.gaps;
+  // a predict with the error covariance on the dense path needs no panel of a launch: its launches write into the panel of all points
+  // (a range-aware one keeps its own panels of delta and writes the panel of all points in a pass of its own: predict_body)
+  const bool shared_panel = cov && !p.sparse;
   if (p.sparse) chunk = std::min<long>(chunk, 131072);  // k_sp_tiles: at most 1024 point blocks per launch
   // tiles of gathered 16-row groups (k_contract_spg) wherever 32-bit LDS-DMA offsets reach every row of the inverse
   p.gathered = p.sparse && h->opt_sparse_rows != 128 && (double)Mp * (double)Mp * 8.0 < 4294967296.0;
@@ -299,7 +306,7 @@ static int plan_predict(mik_handle* h, Plan& p) {
   size_t freeb = 0, totalb = 0;
   HIPC(hipMemGetInfo(&freeb, &totalb));
   const size_t have = h->lane[0].Bt.bytes + h->lane[1].Bt.bytes;
-  while (chunk > 128 && (size_t)chunk * Mp * sizeof(double) * (lanes2_wanted ? 2 : 1) > std::max(freeb + have, have) / 2) chunk = ((chunk / 2 + 127) / 128) * 128;
+  while (!shared_panel && chunk > 128 && (size_t)chunk * Mp * sizeof(double) * (lanes2_wanted ? 2 : 1) > std::max(freeb + have, have) / 2) chunk = ((chunk / 2 + 127) / 128) * 128;
   // equal chunks: ceil(npt / chunk) launches of the same size (a short last launch drains as long as a full one)
   long nchunks = (npt + chunk - 1) / chunk;
   chunk = (((npt + nchunks - 1) / nchunks + 127) / 128) * 128;
@@ -314,7 +321,7 @@ static int plan_predict(mik_handle* h, Plan& p) {
   const size_t nTb = (size_t)chunk / 128;
   for (int L = 0; L < (p.lanes2 ? 2 : 1); ++L) {
     PredictLane& ln = h->lane[L];
-    MIKC(ln.Bt.ensure(sizeof(double) * (size_t)chunk * Mp));
+    if (!shared_panel) MIKC(ln.Bt.ensure(sizeof(double) * (size_t)chunk * Mp));
     MIKC(ln.part.ensure(sizeof(double) * (size_t)chunk * nIblk));
     MIKC(ln.queue.ensure(8 * sizeof(unsigned long long)));
     if (!p.sparse) break;
@@ -338,11 +345,12 @@ static int plan_predict(mik_handle* h, Plan& p) {
 
 // the right-hand sides of launch l into lane ln's panel on stream st, with z of every field; the range-aware path first marks the
 // candidate station tiles of every point block and then writes delta for those only
-static int launch_rhs(mik_handle* h, const Plan& p, const Launch& l, PredictLane& ln, hipStream_t st) {
+// zscratch (a dense plan only): a pass that is there for its panel alone -- z goes to zscratch, no event is recorded
+static int launch_rhs(mik_handle* h, const Plan& p, const Launch& l, PredictLane& ln, hipStream_t st, double* zscratch = nullptr) {
   const LaunchEvents& ev = h->pr_launch[(size_t)l.c];
   const long t0 = l.t0, npt = p.npt;
   RhsArgs a{};
-  a.Bt = ln.Bt.as<double>();
+  a.Bt = p.panel ? p.panel + (size_t)t0 * (size_t)p.Mp : ln.Bt.as<double>();
   a.ld = p.Mp;
   a.palloc = l.palloc;
   a.nvalid = l.nvalid;
@@ -368,10 +376,10 @@ static int launch_rhs(mik_handle* h, const Plan& p, const Launch& l, PredictLane
   a.extra = h->nextra ? h->extra_rows.as<double>() + t0 : nullptr;
   a.extra_stride = npt;
   a.cvec = p.nf > 0 ? (const double*)h->fc.as<double>() : (const double*)h->cvec.as<double>();
-  a.zout = h->z.as<double>() + t0;
+  a.zout = (zscratch ? zscratch : h->z.as<double>()) + t0;
   const dim3 grid(l.palloc / MIK_TP), block(256);
   if (!p.sparse) {
-    HIPC(hipEventRecord(ev.rhs_begin, st));
+    if (!zscratch) HIPC(hipEventRecord(ev.rhs_begin, st));
     if (h->model == MIK_MODEL_CUSTOM) {
       DISPATCH_NDIM_FIXED(7, h->geo ? 1 : h->ndim, k_rhs, grid, block, st, a);
       MIKC(custom_roundtrip(h, a.Bt, l.nvalid, h->N, p.Mp));
@@ -427,7 +435,7 @@ static int launch_rhs(mik_handle* h, const Plan& p, const Launch& l, PredictLane
     else hipLaunchKernelGGL((k_rhs<0, 0, false, false, MIK_FB>), grid, block, 0, st, b);
   }
   HIPC(hipGetLastError());
-  HIPC(hipEventRecord(ev.rhs_end, st));
+  if (!zscratch) HIPC(hipEventRecord(ev.rhs_end, st));
   return MIK_OK;
 }
 
@@ -439,7 +447,7 @@ static int contract_dense(mik_handle* h, const Plan& p, const Launch& l) {
   const int nIblk = p.nIblk, kend = p.kend;
   HIPC(hipEventRecord(ev.contract_begin, sc));
   const double* Ai = h->T.as<double>();
-  const double* Bi = ln.Bt.as<double>();
+  const double* Bi = p.panel ? p.panel + (size_t)l.t0 * (size_t)p.Mp : ln.Bt.as<double>();
   double* pp = ln.part.as<double>();
   const long ldm = p.Mp;
   const unsigned sgrid = (unsigned)super_grid(nIblk, l.nTb);
@@ -809,7 +817,67 @@ static int read_back(mik_handle* h, const Plan& p, bool sorted_now) {
   return MIK_OK;
 }
 
-int one_predict(mik_handle* h) {
+// The error covariance of a predict whose launches have filled the panel of all points (mik_k_cov.h), on the handle's stream behind the
+// last launch: stage 0 (-gamma* above the diagonal), stage 1 (Yt = Bt_all B^T), stage 2 (the upper block triangle, mirrored; the diagonal
+// from sigma^2), then the P x P corner of C leaves row block by row block through two page-locked pieces of about 32 MB: piece i + 1 is
+// on its way while the host copies piece i into the caller's array.  MIK_COV_PROF=1 prints the event-timed stages to stderr.
+static int cov_stages(mik_handle* h, const Plan& p, long Pp, double* Yt, double* C, double* cov_out) {
+  static const bool prof = getenv("MIK_COV_PROF") && atoi(getenv("MIK_COV_PROF")) != 0;
+  const long P = h->npt;
+  hipStream_t st = h->stream;
+  for (hipEvent_t& e : h->ev_cov)
+    if (!e) HIPC(hipEventCreate(&e));
+  PredictLane& ln = h->lane[0];
+  const int nPblk = (int)(Pp / 128);
+  HIPC(hipEventRecord(h->ev_cov[0], st));
+  CovGammaArgs g{};
+  g.px = h->px.as<double>(), g.py = h->py.as<double>(), g.pz = h->ndim == 3 ? h->pz.as<double>() : nullptr;
+  g.npt = P, g.v = h->v, g.eps = h->eps, g.C = C, g.ldc = Pp;
+  const dim3 ggrid((unsigned)P, (unsigned)((P + 255) / 256)), gblock(256);
+  DISPATCH_MODEL_NDIM(h->model, h->geo ? 1 : h->ndim, k_ss_reduce, ggrid, gblock, st, g);
+  HIPC(hipEventRecord(h->ev_cov[1], st));
+  CovGemmArgs a{};
+  a.Bt = p.panel, a.T = h->T.as<double>(), a.Yt = Yt, a.ld = p.Mp, a.C = C, a.ldc = Pp, a.ss = h->ss.as<double>(), a.npt = P;
+  a.nPblk = nPblk, a.nIblk = p.nIblk, a.kend = p.kend, a.queue = ln.queue.as<unsigned long long>();
+  HIPC(hipMemsetAsync(ln.queue.p, 0, 8 * sizeof(unsigned long long), st));
+  hipLaunchKernelGGL((k_ss_reduce<2, 1>), dim3((unsigned)std::min<long>(2L * h->n_cu, super_grid(nPblk, p.nIblk))), dim3(512), 0, st, a);
+  HIPC(hipEventRecord(h->ev_cov[2], st));
+  HIPC(hipMemsetAsync(ln.queue.p, 0, 8 * sizeof(unsigned long long), st));
+  hipLaunchKernelGGL((k_ss_reduce<2, 2>), dim3((unsigned)std::min<long>(2L * h->n_cu, super_grid(nPblk, nPblk))), dim3(512), 0, st, a);
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(h->ev_cov[3], st));
+  const long rb = std::min<long>(Pp, std::max<long>(128, (((32L << 20) / (8 * P)) / 128) * 128));  // rows per piece
+  MIKC(h->pin_cov.ensure(sizeof(double) * 2 * (size_t)rb * (size_t)P));
+  const long npiece = (P + rb - 1) / rb;
+  if (prof) HIPC(hipEventSynchronize(h->ev_cov[3]));  // (the copy's time alone)
+  const auto t0 = std::chrono::steady_clock::now();
+  for (long i = 0; i <= npiece; ++i) {
+    if (i < npiece) {
+      const long r0 = i * rb, rows = std::min(rb, P - r0);
+      HIPC(hipMemcpy2DAsync(h->pin_cov.as<double>() + (size_t)(i & 1) * rb * P, sizeof(double) * P, C + (size_t)r0 * Pp, sizeof(double) * Pp,
+                            sizeof(double) * P, (size_t)rows, hipMemcpyDeviceToHost, st));
+      HIPC(hipEventRecord(h->ev_cov[4 + (i & 1)], st));
+    }
+    if (i > 0) {
+      const long j = i - 1, r0 = j * rb, rows = std::min(rb, P - r0);
+      HIPC(hipEventSynchronize(h->ev_cov[4 + (j & 1)]));
+      host_copy(cov_out + (size_t)r0 * P, h->pin_cov.as<double>() + (size_t)(j & 1) * rb * P, sizeof(double) * (size_t)rows * (size_t)P);
+    }
+  }
+  if (prof) {
+    float m0 = 0.f, m1 = 0.f, m2 = 0.f;
+    HIPC(hipEventElapsedTime(&m0, h->ev_cov[0], h->ev_cov[1]));
+    HIPC(hipEventElapsedTime(&m1, h->ev_cov[1], h->ev_cov[2]));
+    HIPC(hipEventElapsedTime(&m2, h->ev_cov[2], h->ev_cov[3]));
+    const double mc = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    fprintf(stderr, "mik_predict_cov: P %ld Pp %ld Mp %d kend %d stage0_ms %.4f stage1_ms %.4f stage2_ms %.4f copy_ms %.4f\n", P, Pp, p.Mp, p.kend,
+            m0, m1, m2, mc);
+  }
+  return MIK_OK;
+}
+
+// cov_out != nullptr: the predict with the error covariance (one_predict_cov; mik_k_cov.h)
+static int predict_body(mik_handle* h, double* cov_out) {
   if (!h || !h->have_factor) return fail(MIK_ESTATE, "mik_predict: factor first");
   if (!h->have_points) return fail(MIK_ESTATE, "mik_predict: set points first");
   HIPC(hipSetDevice(h->device));
@@ -826,7 +894,15 @@ int one_predict(mik_handle* h) {
     return MIK_OK;
   }
   Plan p{};
-  MIKC(plan_predict(h, p));
+  MIKC(plan_predict(h, p, cov_out != nullptr));
+  const long Pp = ((h->npt + 127) / 128) * 128;
+  DevBuf cov_bt, cov_yt, cov_c, cov_z;  // Bt_all and Yt (Pp x Mp), C (Pp x Pp): this call's, freed after the stream has drained
+  if (cov_out) {
+    MIKC(cov_bt.ensure(sizeof(double) * (size_t)Pp * (size_t)p.Mp));
+    MIKC(cov_yt.ensure(sizeof(double) * (size_t)Pp * (size_t)p.Mp));
+    MIKC(cov_c.ensure(sizeof(double) * (size_t)Pp * (size_t)Pp));
+    if (!p.sparse) p.panel = cov_bt.as<double>();
+  }
   HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));  // an earlier predict's result copies still read z / ss
   if (p.sparse && h->geo) MIKC(geo_point_vectors(h));  // what the candidate boxes of a geographic problem are built from
   // C of the fields first: the second lane starts at ev_predict0, and every k_rhs reads C
@@ -854,8 +930,24 @@ int one_predict(mik_handle* h) {
   if (p.lanes2) HIPC(hipStreamWaitEvent(h->stream, h->ev_lane1, 0));  // the handle's stream ends behind both lanes
   HIPC(hipEventRecord(h->ev_predict1, h->stream));
   HIPC(hipEventRecord(h->ev_d2h, h->stream_d2h));
+  if (cov_out && p.sparse) {
+    // The range-aware predict has run as always -- z and sigma^2 are mik_predict's bits -- but its panels hold delta on the candidate tiles
+    // only: the right-hand sides of all points are written by one more dense k_rhs pass (its z, the dense path's rounding of the same
+    // number, goes to a scratch plane).
+    MIKC(cov_z.ensure(sizeof(double) * (size_t)Pp));
+    Plan d = p;
+    d.sparse = d.gathered = d.sortpts = d.lanes2 = false;
+    d.perm = nullptr, d.nf = 0, d.panel = cov_bt.as<double>();
+    for (long c = 0; c < d.nchunks; ++c) MIKC(launch_rhs(h, d, Launch(d, c), h->lane[0], h->stream, cov_z.as<double>()));
+    p.panel = d.panel;
+  }
+  if (cov_out) MIKC(cov_stages(h, p, Pp, cov_yt.as<double>(), cov_c.as<double>(), cov_out));
   HIPC(hipStreamSynchronize(h->stream));
   MIKC(read_back(h, p, sorted_now));
   h->have_results = true;
   return MIK_OK;
 }
+
+int one_predict(mik_handle* h) { return predict_body(h, nullptr); }
+
+int one_predict_cov(mik_handle* h, double* cov_out) { return predict_body(h, cov_out); }

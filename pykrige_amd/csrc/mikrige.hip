@@ -120,6 +120,9 @@ static void destroy_one(mik_handle* h) {
   h->pin_out.release();
   h->pin_fz.release();
   h->pin_gss.release();
+  h->pin_cov.release();
+  for (hipEvent_t e : h->ev_cov)
+    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->evpool) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->la_events) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ps_events) (void)hipEventDestroy(e);
@@ -1574,6 +1577,38 @@ int mik_predict(mik_handle* h) {
   if (lrc != MIK_OK) return fail(lrc, "device " + std::to_string(h->device) + " (group member 0): " + lerr);
   if (rc != MIK_OK) return fail(rc, err);
   return MIK_OK;
+}
+
+// The predict of the resident points with their error covariance (mik_k_cov.h).  Every refusal comes before anything is launched; a NULL
+// cov_out stops behind them.
+int mik_predict_cov(mik_handle* h, double* cov_out) {
+  if (!h) return fail(MIK_ESTATE, "mik_predict_cov: NULL handle");
+  if (!h->have_problem) return fail(MIK_ESTATE, "mik_predict_cov: set the problem first");
+  if (!h->have_points) return fail(MIK_ESTATE, "mik_predict_cov: set points first");
+  if (h->model == MIK_MODEL_CUSTOM) return fail(MIK_EINVAL, "mik_predict_cov: a custom variogram is evaluated on the host; the covariance between points is not built for it");
+  if (h->pinv) return fail(MIK_EINVAL, "mik_predict_cov: the covariance identity needs a regular inverse (pseudo_inv is set)");
+  if (h->is_kid || !h->kids.empty()) return fail(MIK_EINVAL, "mik_predict_cov: the covariance is not computed by a device group");
+  if (h->masked) return fail(MIK_EINVAL, "mik_predict_cov: masked points have no covariance matrix (set the unmasked points alone)");
+  if (h->npt == 0) return fail(MIK_EINVAL, "mik_predict_cov: no points");
+  if (h->nf > 0 && h->gaps_any) return fail(MIK_EINVAL, "mik_predict_cov: fields with gaps (mik_set_field_gaps) have no common covariance");
+  HIPC(hipSetDevice(h->device));
+  {  // Bt_all and Yt (Pp x Mp) and C (Pp x Pp) within a quarter of device memory, the rule of the gaps' W_all
+    size_t freeb = 0, totalb = 0;
+    HIPC(hipMemGetInfo(&freeb, &totalb));
+    const double quarter = (double)totalb / 4.0, mp = (double)h->Mp;
+    const double pp = (double)(((h->npt + 127) / 128) * 128);
+    if (sizeof(double) * (2.0 * pp * mp + pp * pp) > quarter) {
+      // largest Pp = 128 k with 8 (2 Pp Mp + Pp^2) <= quarter
+      long fit = (long)((std::sqrt(mp * mp + quarter / 8.0) - mp) / 128.0) * 128;
+      while (fit > 0 && sizeof(double) * (2.0 * fit * mp + (double)fit * fit) > quarter) fit -= 128;
+      return fail(MIK_EINVAL, "mik_predict_cov: the buffers of " + std::to_string(h->npt) + " points (two of Pp x " + std::to_string(h->Mp) +
+                                  " and one of Pp x Pp doubles, Pp = " + std::to_string((long)pp) +
+                                  ") would exceed a quarter of device memory; the largest number of points that fits is " + std::to_string(fit));
+    }
+  }
+  if (!cov_out) return MIK_OK;
+  if (!h->have_factor) MIKC(mik_factor(h));
+  return one_predict_cov(h, cov_out);
 }
 
 int mik_predict_moving_window(mik_handle* h, int n_closest) {

@@ -778,6 +778,74 @@ class _KrigingBase:
             zf = np.ma.array(zf, mask=np.zeros(zf.shape, dtype=bool))
         return zf.reshape((nf,) + tuple(shape)), ss
 
+    # ---------------------------------------------------------------- error covariance between prediction points (mik_predict_cov)
+    _COV_DOC = """Kriged values and the kriging error covariance between the prediction points.
+
+        ``zvalues, cov = obj.execute_cov(style, xpoints, ypoints[, zpoints], backend="vectorized", specified_drift_arrays=None)``
+
+        ``style`` is ``'points'`` or ``'grid'``.  ``zvalues`` is what ``execute()`` returns first for the same call (same shape, type and
+        bits).  ``cov`` is a C-contiguous float64 ndarray of shape ``(P, P)``, ``P = prod(zvalues.shape)``, in the flattened order of
+        ``zvalues``; it is exactly symmetric and ``diag(cov)`` is ``execute()``'s ``sigmasq`` bit for bit.  It is what the standard error of
+        an areal mean, a total or a difference needs (``w @ cov @ w``) and what conditional realisations are drawn from; scikit-learn calls
+        it ``predict(return_cov=True)``.
+
+        The identity.  For points p, q let ``b(.)`` be the right-hand sides exactly as ``execute()`` forms them (drift rows, the border
+        row and the ``exact_values`` zeroing included) and ``e_p = Z(p) - zhat(p)``.  Then
+        ``cov(e_p, e_q) = -gamma*(d_pq) - b(p)^T A^-1 b(q)`` with ``gamma*(d) = 0 if d <= eps`` (the library's exact-hit eps) and the
+        object's variogram at ``d`` otherwise; ``d_pq`` is the distance between the adjusted points (geographic coordinates: the
+        great-circle distance).  It holds for ordinary and universal kriging alike; ``p = q`` is ``sigmasq = -b^T A^-1 b``, and with
+        ``exact_values=True`` the rows of points that sit on a station are zero.  Everything comes from the one resident inverse: two
+        matrix products on the device, ``2 P M^2 + P^2 M`` flop for a kriging matrix of order M, and ``P^2`` doubles copied back.
+
+        ``specified_drift_arrays`` is the universal-kriging classes' argument of ``execute()``; the ordinary classes accept only
+        ``None``.  There is no ``n_closest_points``: the windows of a moving window differ from point to point, so no joint covariance
+        exists.  ``style='masked'`` raises ``ValueError`` (set the unmasked points as ``'points'``), any other unknown style and an
+        empty point list raise ``ValueError``, ``variogram_model='custom'`` raises ``NotImplementedError`` (the callable runs on the
+        host), ``pseudo_inv=True`` raises ``ValueError`` (the identity needs a regular inverse), a handle that spans a device group
+        raises ``ValueError``, and a ``P`` whose device buffers (two of ``P x M`` and one of ``P x P`` doubles, rounded up to 128) would
+        exceed a quarter of device memory raises ``ValueError`` naming the largest ``P`` that fits.  ``execute()`` and
+        ``execute_fields()`` are untouched: a call after ``execute_cov`` returns the bits it returned before."""
+
+    def _execute_cov(self, style, axes, backend, specified_drift_arrays, universal):
+        """execute_cov of the four classes: every argument is checked on the host before the device is touched."""
+        if style == "masked":
+            raise ValueError("execute_cov: style 'masked' has no covariance matrix; pass the unmasked points as style 'points'")
+        if style != "grid" and style != "points":
+            raise ValueError("style argument must be 'grid' or 'points'")
+        self._check_backend(backend, None)
+        if not universal and specified_drift_arrays is not None:
+            raise ValueError("execute_cov: specified_drift_arrays belongs to the universal-kriging classes")
+        if self.variogram_model == "custom":
+            raise NotImplementedError("execute_cov: variogram_model='custom' is evaluated on the host; the covariance between points is not built for it")
+        if self.pseudo_inv:
+            raise ValueError("execute_cov needs a regular inverse: the covariance identity does not hold for pseudo_inv=True")
+        if self._handle is not None and self._handle.n_devices > 1:
+            raise ValueError("execute_cov: this object's handle spans a device group of %d devices; the covariance is computed on one "
+                             "device" % self._handle.n_devices)
+        P = self._prepare(style, axes, None, **(dict(specified_drift_arrays=specified_drift_arrays, backend=backend) if universal else {}))
+        if P.npt == 0:
+            raise ValueError("execute_cov: no points")
+        # _upload_and_factor without its factor(): mik_predict_cov refuses (an oversized P among the reasons) before it launches anything
+        # and factors itself if no factor is resident
+        h = self._get_handle()
+        if h.n_devices > 1:
+            raise ValueError("execute_cov: this object's handle spans a device group of %d devices; the covariance is computed on one "
+                             "device" % h.n_devices)
+        key = self._problem_key()
+        if key is not None:
+            key = (key, h.option_epoch)
+        self.factor_reused = key is not None and key == getattr(self, "_factor_key", None)
+        if not self.factor_reused:
+            self._set_problem(h)
+        self._max_points = max(self._max_points, P.npt)
+        P.load(h, self._ndim)
+        cov = h.predict_cov()
+        self._factor_key = key
+        self.last_timing = h.timing()
+        z, ss = h.get_results()
+        z, _ = self._finish(z, ss, style, P.shape, None, backend)
+        return z, cov
+
     # ---------------------------------------------------------------- leave-one-out cross-validation (mik_cross_validate)
     _CV_DOC = """Leave-one-out cross-validation on the device: every station kriged from the other stations.
 
@@ -980,6 +1048,11 @@ class OrdinaryKriging(_KrigingBase):
 
     execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
 
+    def execute_cov(self, style, xpoints, ypoints, backend="vectorized", specified_drift_arrays=None):
+        return self._execute_cov(style, (xpoints, ypoints), backend, specified_drift_arrays, False)
+
+    execute_cov.__doc__ = _KrigingBase._COV_DOC
+
 
 # =====================================================================================================
 class UniversalKriging(OrdinaryKriging):
@@ -1109,6 +1182,11 @@ class UniversalKriging(OrdinaryKriging):
 
     execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
 
+    def execute_cov(self, style, xpoints, ypoints, backend="vectorized", specified_drift_arrays=None):
+        return self._execute_cov(style, (xpoints, ypoints), backend, specified_drift_arrays, True)
+
+    execute_cov.__doc__ = _KrigingBase._COV_DOC
+
     def _grid_rows(self, style, axes, shape, mask, specified_drift_arrays, backend):
         rows = []
         if self.external_Z_drift:  # looked up at the ORIGINAL coordinates (uk.py:967-971): the host meshgrid, for this term only
@@ -1224,6 +1302,11 @@ class OrdinaryKriging3D(_KrigingBase):
 
     execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
 
+    def execute_cov(self, style, xpoints, ypoints, zpoints, backend="vectorized", specified_drift_arrays=None):
+        return self._execute_cov(style, (xpoints, ypoints, zpoints), backend, specified_drift_arrays, False)
+
+    execute_cov.__doc__ = _KrigingBase._COV_DOC
+
 
 # =====================================================================================================
 class UniversalKriging3D(OrdinaryKriging3D):
@@ -1305,6 +1388,11 @@ class UniversalKriging3D(OrdinaryKriging3D):
                                     dict(specified_drift_arrays=specified_drift_arrays), valid=valid)
 
     execute_fields.__doc__ = _KrigingBase._FIELDS_DOC
+
+    def execute_cov(self, style, xpoints, ypoints, zpoints, backend="vectorized", specified_drift_arrays=None):
+        return self._execute_cov(style, (xpoints, ypoints, zpoints), backend, specified_drift_arrays, True)
+
+    execute_cov.__doc__ = _KrigingBase._COV_DOC
 
     def _grid_rows(self, style, axes, shape, mask, specified_drift_arrays, backend):
         rows = self._spec_rows(style, shape, int(np.prod(shape)), specified_drift_arrays)
