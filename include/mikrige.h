@@ -447,6 +447,27 @@ int  mik_cross_validate_folds(mik_handle *h, const int32_t *fold /* n */, int nf
  * that fits). */
 int  mik_predict_cov(mik_handle *h, double *cov_out /* npt x npt, row-major */);
 
+/* Block kriging: the resident points are block centres, and every block is kriged as the arithmetic mean of Z over its nd discretisation
+ * nodes (ABI 9, added without a version step: a library without the symbol is stale).  offsets holds the nd node offsets from a centre,
+ * nd x ndim doubles, row-major, in the ADJUSTED coordinates the resident points are in (the anisotropy adjustment is linear: offset u of
+ * the caller's block becomes stretch . rot . u, the same for every block).  With b(.) the right-hand side exactly as mik_predict forms it at a
+ * node (drift rows, the border row and the exact_values zeroing -- decided node by node -- included) and B = A^-1,
+ *     bbar = (sum_u b(centre + offset_u)) / nd                 summed in node order, one division,
+ *     z_V = c . bbar,     sigma^2_V = -gbar - bbar^T B bbar,
+ *     gbar = (sum_u sum_v gamma*(|offset_u - offset_v|)) / nd^2,     gamma*(d) = 0 if d <= eps (mik_problem.eps), else the variogram at d:
+ * the estimate and the error variance of the mean of Z over the nodes -- the mean of the matching nd x nd block of mik_predict_cov's matrix,
+ * without that matrix.  A nugget counts as variation of Z itself and averages down with nd.  Regional-linear drift rows take the mean of the
+ * node coordinates, point_log rows the mean of the well term at the nodes (both on the device); the resident points' extra_rows, if any, are
+ * taken as already averaged over the nodes by the caller.
+ * On the device (mik_k_block.h) a further form of k_rhs writes bbar -- per station column a loop over the nodes, the offsets in LDS, nd
+ * variogram values per station and block --, the dense contraction runs unchanged (always the dense path, also on a factor in Hilbert-curve
+ * order: "sparse" reads 0 in mik_timing), one workgroup forms gbar once per call and a pass behind the reduce subtracts it.  nd = 1 with a zero offset is
+ * mik_predict's dense result bit for bit; the results do not depend on how "chunk" cuts the call into launches.  Results come back through
+ * mik_get_results / mik_take_results as after mik_predict.  Factors if no factor is resident.
+ * MIK_EINVAL, before anything is launched: nd < 1, nd > 512, a NULL or non-finite offset, geographic coordinates, a custom variogram,
+ * pseudo_inv, a handle that spans a device group, value fields or gaps being set. */
+int  mik_predict_block(mik_handle *h, const double *offsets /* nd x ndim, ADJUSTED */, int nd);
+
 /* Variogram-fit statistics: replaces core._find_statistics -> core._krige (core.py:759-836, 654-756): for
  * i = 1..n-1 station i is kriged from stations 0..i-1.  k_out / ss_out have n entries (entry 0 unused = 0). */
 int  mik_statistics(mik_handle *h, double *k_out, double *ss_out);

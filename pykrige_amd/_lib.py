@@ -101,6 +101,7 @@ SIGNATURES = {
     "mik_synchronize": (C.c_int, [C.c_void_p]),
     "mik_set_custom_variogram": (C.c_int, [C.c_void_p, VARIOGRAM_FN, C.c_void_p]),
     "mik_predict_cov": (C.c_int, [C.c_void_p, _dp]),
+    "mik_predict_block": (C.c_int, [C.c_void_p, _dp, C.c_int]),
     "mik_predict_moving_window": (C.c_int, [C.c_void_p, C.c_int]),
     "mik_cross_validate": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "mik_cross_validate_folds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, _dp, _dp]),
@@ -374,6 +375,15 @@ class Handle:
         cov = np.empty((n, n), dtype=np.float64)
         check(self._lib.mik_predict_cov(self._h, _ptr(cov)))
         return cov
+
+    def predict_block(self, offsets):
+        """mik_predict_block: the resident points as block centres, every block the mean of Z over its nodes.  offsets: (nd, ndim) node
+        offsets in the adjusted coordinates.  z and sigma^2 come back through get_results, as after predict."""
+        self._taken = None
+        off = np.ascontiguousarray(offsets, dtype=np.float64)
+        if off.ndim != 2:
+            raise ValueError("offsets must have shape (nd, ndim)")
+        check(self._lib.mik_predict_block(self._h, _ptr(off), int(off.shape[0])))
 
     def predict_moving_window(self, n_closest_points):
         self._taken = None

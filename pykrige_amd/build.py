@@ -29,7 +29,7 @@ COMMON = ["mik_host.h", "mik_dev.h"]
 UNITS = {
     "mikrige": ("mikrige.hip", ["mik_k_core.h"], []),
     "mik_inverse": ("mik_inverse.hip", ["mik_k_inverse.h"], []),
-    "mik_predict": ("mik_predict.hip", ["mik_k_predict.h", "mik_k_fields.h", "mik_k_cvfolds.h", "mik_k_gaps.h", "mik_k_cov.h"], []),
+    "mik_predict": ("mik_predict.hip", ["mik_k_predict.h", "mik_k_fields.h", "mik_k_cvfolds.h", "mik_k_gaps.h", "mik_k_cov.h", "mik_k_block.h"], []),
     "mik_mw": ("mik_mw.hip", ["mik_k_mw.h", "mik_k_mw_chol.h"], []),
     "mik_mw_solve": ("mik_mw_solve.hip", ["mik_k_mw_solve.h", "mik_k_mw_chol.h"], []),
     "mik_mw_chol0": ("mik_mw_chol.hip", ["mik_k_mw_chol.h"], ["-DMIK_MWC_PART=0"]),

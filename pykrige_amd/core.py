@@ -55,6 +55,56 @@ def anisotropy_matrices(ndim, scaling, angle):
     return np.dot(rot_z, np.dot(rot_y, rot_x)), np.array([1.0, scaling[0], scaling[1]], dtype=np.float64)
 
 
+BLOCK_MAX_NODES = 512  # mik_predict_block: the node offsets of a block live in LDS
+
+
+def block_node_offsets(ndim, block_size, n_disc):
+    """(nd, ndim) offsets of a block's discretisation nodes from its centre, in the caller's raw coordinates: cell-centred and regular as
+    in GSLIB's kt3d (nxdis, nydis, nzdis) -- along an axis of length L with n nodes ((i + 0.5) / n - 0.5) L -- in node order, x fastest,
+    then y, then z.  block_size: a positive scalar or one per axis; n_disc: a positive int or one per axis; nd = prod(n_disc) <= 512."""
+    import operator
+
+    def per_axis(v, name, conv):
+        if np.ndim(v) == 0:
+            return [conv(v)] * ndim
+        v = list(np.asarray(v).ravel()) if isinstance(v, np.ndarray) else list(v)
+        if len(v) != ndim:
+            raise ValueError("%s must be a scalar or have one value per axis (%d); got %d values" % (name, ndim, len(v)))
+        return [conv(x) for x in v]
+
+    def as_int(x):
+        try:
+            return operator.index(x)
+        except TypeError:
+            raise ValueError("n_disc must be a positive int or one positive int per axis; got %r" % (x,)) from None
+
+    def as_len(x):
+        try:
+            return float(x)
+        except (TypeError, ValueError):
+            raise ValueError("block_size must be a positive number or one positive number per axis; got %r" % (x,)) from None
+
+    size = per_axis(block_size, "block_size", as_len)
+    n = per_axis(n_disc, "n_disc", as_int)
+    if not all(np.isfinite(v) and v > 0.0 for v in size):
+        raise ValueError("block_size must be positive and finite; got %r" % (block_size,))
+    if not all(v >= 1 for v in n):
+        raise ValueError("n_disc must be positive; got %r" % (n_disc,))
+    nd = int(np.prod(n, dtype=np.int64))
+    if nd > BLOCK_MAX_NODES:
+        raise ValueError("n_disc = %r gives %d nodes per block; at most %d are built" % (n_disc, nd, BLOCK_MAX_NODES))
+    ax = [((np.arange(k, dtype=np.float64) + 0.5) / k - 0.5) * L for k, L in zip(n, size)]
+    grids = np.meshgrid(*reversed(ax), indexing="ij")  # the last axis varies slowest
+    return np.stack([g.ravel() for g in reversed(grids)], axis=1)
+
+
+def adjust_offsets(off, ndim, scaling, angle):
+    """Node offsets in the adjusted coordinates: the anisotropy adjustment is linear, an adjusted node is adjusted centre + T u with
+    T = stretch . rot (the matrices of adjust_for_anisotropy)."""
+    rot, stretch = anisotropy_matrices(ndim, scaling, angle)
+    return np.ascontiguousarray(np.dot(np.diag(stretch), np.dot(rot, np.asarray(off, dtype=np.float64).T)).T)
+
+
 def great_circle_distance(lon1, lat1, lon2, lat2):
     """Great-circle distance in degrees, arctan form (core.py:36-97) -- host twin of the device functor
     gc_dist; used by the constructor-time variogram fit only."""

@@ -512,6 +512,7 @@ int sort_points(mik_handle* h, long chunk, long nchunks);                       
 int upload_fields(mik_handle* h, int want);                                                                      // mik_predict.hip
 int one_predict(mik_handle* h);                                                                                  // mik_predict.hip
 int one_predict_cov(mik_handle* h, double* cov_out);                                                             // mik_predict.hip
+int one_predict_block(mik_handle* h, const double* offsets, int nd);                                             // mik_predict.hip
 int one_predict_mw(mik_handle* h, int n_closest);
 int one_get_field_sigmasq(mik_handle* h, double* out, long ntot);                                                // mik_predict.hip
 int one_cross_validate(mik_handle* h, double* zhat_out, double* ss_out);                                         // mik_predict.hip

@@ -951,3 +951,120 @@ static int predict_body(mik_handle* h, double* cov_out) {
 int one_predict(mik_handle* h) { return predict_body(h, nullptr); }
 
 int one_predict_cov(mik_handle* h, double* cov_out) { return predict_body(h, cov_out); }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Block kriging (mik_predict_block; mik_k_block.h).  A path of its own beside predict_body: the plan, the dense contraction, the copies
+// and the timing are the point predict's functions, called as they are; the right-hand sides (bbar), gbar and the pass that subtracts
+// it are the block's.
+#include "mik_k_block.h"
+
+// the six named models x NDIM 2 / 3 -- no geographic form, no custom variogram
+#define DISPATCH_BLOCK_NDIM(model, NDIM, KERNEL, grid, block, stream, args)                          \
+  switch (model) {                                                                                   \
+    case 0: hipLaunchKernelGGL((KERNEL<0, NDIM>), grid, block, 0, stream, args); break;              \
+    case 1: hipLaunchKernelGGL((KERNEL<1, NDIM>), grid, block, 0, stream, args); break;              \
+    case 2: hipLaunchKernelGGL((KERNEL<2, NDIM>), grid, block, 0, stream, args); break;              \
+    case 3: hipLaunchKernelGGL((KERNEL<3, NDIM>), grid, block, 0, stream, args); break;              \
+    case 4: hipLaunchKernelGGL((KERNEL<4, NDIM>), grid, block, 0, stream, args); break;              \
+    default: hipLaunchKernelGGL((KERNEL<5, NDIM>), grid, block, 0, stream, args); break;             \
+  }
+#define DISPATCH_BLOCK(model, ndim, KERNEL, grid, block, stream, args)                               \
+  do {                                                                                               \
+    if ((ndim) == 3) { DISPATCH_BLOCK_NDIM(model, 3, KERNEL, grid, block, stream, args) }            \
+    else { DISPATCH_BLOCK_NDIM(model, 2, KERNEL, grid, block, stream, args) }                        \
+  } while (0)
+
+// bbar of launch l into lane 0's panel on the handle's stream, with z (the dense branch of launch_rhs with the node offsets)
+static int launch_rhs_block(mik_handle* h, const Plan& p, const Launch& l, const double* off, int nd) {
+  const LaunchEvents& ev = h->pr_launch[(size_t)l.c];
+  const long t0 = l.t0;
+  hipStream_t st = h->stream;
+  BlockRhsArgs ba{};
+  RhsArgs& a = ba.r;
+  a.Bt = h->lane[0].Bt.as<double>();
+  a.ld = p.Mp;
+  a.palloc = l.palloc;
+  a.nvalid = l.nvalid;
+  a.px = h->px.as<double>() + t0;
+  a.py = h->py.as<double>() + t0;
+  a.pz = h->ndim == 3 ? h->pz.as<double>() + t0 : nullptr;
+  a.N = h->N;
+  a.p = h->p;
+  a.M = h->M;
+  a.Mp = p.Mp;
+  a.ndim = h->ndim;
+  a.xs = h->factor_sorted ? h->xs_s.as<double>() : h->xs.as<double>();
+  a.ys = h->factor_sorted ? h->ys_s.as<double>() : h->ys.as<double>();
+  a.zs = h->factor_sorted ? h->zs_s.as<double>() : h->zs.as<double>();
+  a.dsc = h->factor_eq ? h->dsc.as<double>() : nullptr;
+  a.v = h->v;
+  a.exact = h->exact;
+  a.eps = h->eps;
+  a.rl = h->rl;
+  a.nwells = h->nwells;
+  a.nextra = h->nextra;
+  a.wells = h->wells.as<double>();
+  a.extra = h->nextra ? h->extra_rows.as<double>() + t0 : nullptr;
+  a.extra_stride = p.npt;
+  a.cvec = h->cvec.as<double>();
+  a.zout = h->z.as<double>() + t0;
+  ba.off = off, ba.nd = nd;
+  const dim3 grid(l.palloc / MIK_TP), block(256);
+  HIPC(hipEventRecord(ev.rhs_begin, st));
+  DISPATCH_BLOCK(h->model, h->ndim, k_rhs, grid, block, st, ba);
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(ev.rhs_end, st));
+  return MIK_OK;
+}
+
+int one_predict_block(mik_handle* h, const double* offsets, int nd) {
+  if (!h || !h->have_factor) return fail(MIK_ESTATE, "mik_predict_block: factor first");
+  if (!h->have_points) return fail(MIK_ESTATE, "mik_predict_block: set points first");
+  HIPC(hipSetDevice(h->device));
+  h->tm.rhs_ms = h->tm.contract_ms = h->tm.predict_ms = 0.0;
+  h->tm.contract_launches = 0;
+  h->tm.contract_flops_executed = 0.0;
+  h->tm.symmetric = h->opt_sym;
+  h->tm.engine = 0;
+  h->tm.mw_kernel = 0;
+  h->nf_done = h->nf;
+  h->gap_plane.clear();
+  if (h->npt == 0) {
+    h->have_results = true;
+    return MIK_OK;
+  }
+  Plan p{};
+  MIKC(plan_predict(h, p, false));
+  // always the dense path, also on a factor in Hilbert-curve order (as the gaps predict): sigma^2 = 2 s - delta^T A_inv delta is an
+  // identity of one point's right-hand side, not of a mean of them.  The lane's panel, partial sums and queue are sized either way.
+  p.sparse = p.gathered = p.sortpts = p.lanes2 = false;
+  p.perm = nullptr;
+  h->tm.sparse = h->tm.sparse_ktile = h->tm.sparse_rows = h->tm.points_sorted = 0;
+  const size_t noff = (size_t)nd * (size_t)h->ndim;
+  DevBuf blk;  // the node offsets and, behind them, gbar: this call's, freed after the stream has drained
+  MIKC(blk.ensure(sizeof(double) * (noff + 1)));
+  HIPC(hipMemcpy(blk.p, offsets, sizeof(double) * noff, hipMemcpyHostToDevice));
+  const double* off = blk.as<double>();
+  double* gbar = blk.as<double>() + noff;
+  HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));  // an earlier predict's result copies still read z / ss
+  HIPC(hipEventRecord(h->ev_predict0, h->stream));
+  {  // gbar does not depend on the block: once per call, one workgroup
+    BlockGammaArgs g{};
+    g.off = off, g.nd = nd, g.v = h->v, g.eps = h->eps, g.gbar = gbar;
+    DISPATCH_BLOCK(h->model, h->ndim, k_ss_reduce, dim3(1), dim3(256), h->stream, g);
+  }
+  for (long c = 0; c < p.nchunks; ++c) {
+    const Launch l(p, c);
+    MIKC(launch_rhs_block(h, p, l, off, nd));
+    MIKC(contract_dense(h, p, l));
+    hipLaunchKernelGGL(k_ss_reduce, dim3((l.nvalid + 255) / 256), dim3(256), 0, h->stream, h->ss.as<double>() + l.t0, l.nvalid, (const double*)gbar);
+    MIKC(copy_out(h, p, l, h->stream));
+  }
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(h->ev_predict1, h->stream));
+  HIPC(hipEventRecord(h->ev_d2h, h->stream_d2h));
+  HIPC(hipStreamSynchronize(h->stream));
+  MIKC(read_back(h, p, false));
+  h->have_results = true;
+  return MIK_OK;
+}

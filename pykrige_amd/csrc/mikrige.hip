@@ -1611,6 +1611,24 @@ int mik_predict_cov(mik_handle* h, double* cov_out) {
   return one_predict_cov(h, cov_out);
 }
 
+// Block kriging of the resident points as block centres (mik_k_block.h).  Every refusal comes before anything is launched.
+int mik_predict_block(mik_handle* h, const double* offsets, int nd) {
+  if (!h) return fail(MIK_ESTATE, "mik_predict_block: NULL handle");
+  if (!h->have_problem) return fail(MIK_ESTATE, "mik_predict_block: set the problem first");
+  if (!h->have_points) return fail(MIK_ESTATE, "mik_predict_block: set points first");
+  if (nd < 1 || nd > 512) return fail(MIK_EINVAL, "mik_predict_block: nd = " + std::to_string(nd) + " discretisation nodes; 1 to 512 are built");
+  if (!offsets) return fail(MIK_EINVAL, "mik_predict_block: no node offsets");
+  if (h->geo) return fail(MIK_EINVAL, "mik_predict_block: geographic coordinates (the blocks of a lon / lat grid are not congruent)");
+  if (h->model == MIK_MODEL_CUSTOM) return fail(MIK_EINVAL, "mik_predict_block: a custom variogram is evaluated on the host; block kriging is not built for it");
+  if (h->pinv) return fail(MIK_EINVAL, "mik_predict_block: the block variance needs a regular inverse (pseudo_inv is set)");
+  if (h->is_kid || !h->kids.empty()) return fail(MIK_EINVAL, "mik_predict_block: blocks are not kriged by a device group");
+  if (h->nf > 0 || h->gaps_any) return fail(MIK_EINVAL, "mik_predict_block: value fields (mik_set_fields / mik_set_field_gaps) are set; blocks are kriged from the problem's values");
+  for (long i = 0; i < (long)nd * h->ndim; ++i)
+    if (!std::isfinite(offsets[i])) return fail(MIK_EINVAL, "mik_predict_block: a node offset is not finite");
+  if (!h->have_factor) MIKC(mik_factor(h));
+  return one_predict_block(h, offsets, nd);
+}
+
 int mik_predict_moving_window(mik_handle* h, int n_closest) {
   if (!h) return fail(MIK_ESTATE, "mik_predict_moving_window: NULL handle");
   if (h->gaps_any) return fail(MIK_EINVAL, "mik_predict_moving_window: fields with gaps (mik_set_field_gaps) are kriged by mik_predict only");

@@ -846,6 +846,91 @@ class _KrigingBase:
         z, _ = self._finish(z, ss, style, P.shape, None, backend)
         return z, cov
 
+    # ---------------------------------------------------------------- block kriging of cell averages (mik_predict_block)
+    _BLOCK_DOC = """Block kriging: the kriged average over a block around every point, and its error variance.
+
+        ``zvalues, sigmasq = obj.execute_block(style, xpoints, ypoints[, zpoints], block_size, n_disc=4, backend="vectorized")``
+
+        ``style`` is ``'grid'`` or ``'points'``; the points are the block CENTRES, and ``zvalues`` and ``sigmasq`` have the shape and
+        type ``execute()`` returns for the same call.  ``block_size`` is a positive scalar or one value per axis: the block's edge
+        lengths in the caller's raw coordinates.  ``n_disc`` is a positive int or one per axis: the block is discretised into
+        ``nd = prod(n_disc)`` nodes, ``nd <= 512``, cell-centred and regular as GSLIB's ``kt3d`` places them (``nxdis``, ``nydis``,
+        ``nzdis``): along an axis of length ``L`` with ``n`` nodes the offsets from the centre are ``((i + 0.5) / n - 0.5) L``; node
+        order is x fastest, then y, then z.  The anisotropy adjustment is linear, so an adjusted node is the adjusted centre plus
+        ``T u`` with ``T = stretch . rot``: the ``nd`` adjusted offsets are formed once per call, and the centres take the path of
+        ``execute()``.
+
+        The definition.  With ``b(.)`` the right-hand side exactly as ``execute()`` forms it at a node (the ``exact_values`` zeroing
+        where a node is within ``eps`` of a station, drift rows and the border row included),
+        ``bbar = (sum_u b(node_u)) / nd`` (summed in node order, one division), ``z_V = c . bbar`` and
+        ``sigma^2_V = -gbar - bbar^T A^-1 bbar`` with ``gbar = (sum_u sum_v gamma*(|T (u - v)|)) / nd^2``, ``gamma*(d) = 0 if d <= eps``
+        and the object's variogram otherwise.  This is exactly the estimate, and the error variance, of the ARITHMETIC MEAN of ``Z``
+        over the block's ``nd`` nodes: the same quantity as the mean of the matching ``nd x nd`` block of ``execute_cov``'s matrix on
+        the nodes (and ``zvalues`` is the mean of its ``z``), without that matrix and at one contraction per block instead of one per
+        node.  A nugget is therefore treated as variation of ``Z`` itself: it averages down with ``nd`` (it is not measurement
+        error that a block average would be free of).  ``n_disc=1`` is ``execute()`` at the centres.
+
+        Drift terms: ``regional_linear`` takes the mean of the node coordinates and ``point_log`` the mean of the well term at the
+        nodes, both on the device; ``functional`` drift callables are evaluated on the host at the adjusted nodes and averaged in node
+        order.  ``external_Z`` and ``specified`` drifts raise ``NotImplementedError``.  ``style='masked'`` and any unknown style
+        raise ``ValueError``; a non-positive or wrong-length ``block_size`` or ``n_disc`` and ``nd > 512`` raise ``ValueError``;
+        ``coordinates_type='geographic'`` raises ``ValueError`` (the blocks of a lon / lat grid are not congruent);
+        ``pseudo_inv=True`` raises ``ValueError``; a handle that spans a device group raises ``ValueError``;
+        ``variogram_model='custom'`` raises ``NotImplementedError``.  There is no ``n_closest_points``.  ``execute()``,
+        ``execute_fields()``, ``execute_cov()`` and ``cross_validate()`` are untouched: a call after ``execute_block`` returns the bits
+        it returned before."""
+
+    def _execute_block(self, style, axes, block_size, n_disc, backend):
+        """execute_block of the four classes: every argument is checked on the host before the device is touched."""
+        if style == "masked":
+            raise ValueError("execute_block: style 'masked' is not built; pass the unmasked block centres as style 'points'")
+        if style != "grid" and style != "points":
+            raise ValueError("style argument must be 'grid' or 'points'")
+        self._check_backend(backend, None)
+        off = core.block_node_offsets(self._ndim, block_size, n_disc)
+        if getattr(self, "coordinates_type", "euclidean") == "geographic":
+            raise ValueError("execute_block: coordinates_type='geographic' is not built (the blocks of a lon / lat grid are not congruent)")
+        if self.variogram_model == "custom":
+            raise NotImplementedError("execute_block: variogram_model='custom' is evaluated on the host; block kriging is not built for it")
+        if self.pseudo_inv:
+            raise ValueError("execute_block needs a regular inverse: the block variance is not defined for pseudo_inv=True")
+        if getattr(self, "external_Z_drift", False) or getattr(self, "specified_drift", False):
+            raise NotImplementedError("execute_block: external_Z and specified drifts are given point by point; their block averages are not built")
+        if self._handle is not None and self._handle.n_devices > 1:
+            raise ValueError("execute_block: this object's handle spans a device group of %d devices; blocks are kriged on one device"
+                             % self._handle.n_devices)
+        off = core.adjust_offsets(off, self._ndim, self._scaling(), self._angle())
+        P = self._prepare(style, axes, None)
+        if getattr(self, "functional_drift", False) and P.npt:
+            # the callables at the adjusted nodes (centre + T u), averaged in node order: the points' extra_rows, already averaged
+            ctr = np.asarray(P.arrays, dtype=np.float64)
+            rows = []
+            for f in self.functional_drift_terms:
+                acc = None
+                for u in off:
+                    v = np.asarray(f(*[ctr[:, k] + u[k] for k in range(self._ndim)]), dtype=np.float64)
+                    acc = v if acc is None else acc + v
+                rows.append(acc / float(off.shape[0]))
+            P.extra = np.array(rows, dtype=np.float64)
+        # as _execute_cov: mik_predict_block refuses before it launches anything and factors itself if no factor is resident
+        h = self._get_handle()
+        if h.n_devices > 1:
+            raise ValueError("execute_block: this object's handle spans a device group of %d devices; blocks are kriged on one device"
+                             % h.n_devices)
+        key = self._problem_key()
+        if key is not None:
+            key = (key, h.option_epoch)
+        self.factor_reused = key is not None and key == getattr(self, "_factor_key", None)
+        if not self.factor_reused:
+            self._set_problem(h)
+        self._max_points = max(self._max_points, P.npt)
+        P.load(h, self._ndim)
+        h.predict_block(off)
+        self._factor_key = key
+        self.last_timing = h.timing()
+        z, ss = h.get_results()
+        return self._finish(z, ss, style, P.shape, None, backend)
+
     # ---------------------------------------------------------------- leave-one-out cross-validation (mik_cross_validate)
     _CV_DOC = """Leave-one-out cross-validation on the device: every station kriged from the other stations.
 
@@ -1053,6 +1138,11 @@ class OrdinaryKriging(_KrigingBase):
 
     execute_cov.__doc__ = _KrigingBase._COV_DOC
 
+    def execute_block(self, style, xpoints, ypoints, block_size, n_disc=4, backend="vectorized"):
+        return self._execute_block(style, (xpoints, ypoints), block_size, n_disc, backend)
+
+    execute_block.__doc__ = _KrigingBase._BLOCK_DOC
+
 
 # =====================================================================================================
 class UniversalKriging(OrdinaryKriging):
@@ -1187,6 +1277,11 @@ class UniversalKriging(OrdinaryKriging):
 
     execute_cov.__doc__ = _KrigingBase._COV_DOC
 
+    def execute_block(self, style, xpoints, ypoints, block_size, n_disc=4, backend="vectorized"):
+        return self._execute_block(style, (xpoints, ypoints), block_size, n_disc, backend)
+
+    execute_block.__doc__ = _KrigingBase._BLOCK_DOC
+
     def _grid_rows(self, style, axes, shape, mask, specified_drift_arrays, backend):
         rows = []
         if self.external_Z_drift:  # looked up at the ORIGINAL coordinates (uk.py:967-971): the host meshgrid, for this term only
@@ -1307,6 +1402,11 @@ class OrdinaryKriging3D(_KrigingBase):
 
     execute_cov.__doc__ = _KrigingBase._COV_DOC
 
+    def execute_block(self, style, xpoints, ypoints, zpoints, block_size, n_disc=4, backend="vectorized"):
+        return self._execute_block(style, (xpoints, ypoints, zpoints), block_size, n_disc, backend)
+
+    execute_block.__doc__ = _KrigingBase._BLOCK_DOC
+
 
 # =====================================================================================================
 class UniversalKriging3D(OrdinaryKriging3D):
@@ -1393,6 +1493,11 @@ class UniversalKriging3D(OrdinaryKriging3D):
         return self._execute_cov(style, (xpoints, ypoints, zpoints), backend, specified_drift_arrays, True)
 
     execute_cov.__doc__ = _KrigingBase._COV_DOC
+
+    def execute_block(self, style, xpoints, ypoints, zpoints, block_size, n_disc=4, backend="vectorized"):
+        return self._execute_block(style, (xpoints, ypoints, zpoints), block_size, n_disc, backend)
+
+    execute_block.__doc__ = _KrigingBase._BLOCK_DOC
 
     def _grid_rows(self, style, axes, shape, mask, specified_drift_arrays, backend):
         rows = self._spec_rows(style, shape, int(np.prod(shape)), specified_drift_arrays)
