@@ -347,7 +347,7 @@ void mik_release_results(double *z);                       /* gives such a buffe
  * mik_set_fields hands the handle nf fields of n values, FIELD-MAJOR (field f is values + f * n, the same station order as
  * mik_problem.values); nf = 0 clears them and the handle behaves exactly as without.  The fields are copied (every member of a
  * device group gets them) and stay until the next mik_set_fields or mik_set_problem (which clears them).  With fields set,
- * mik_predict forms C = A_inv[:, :n] V (Mp x nf) on every device from that device's own copy of the inverse (k_cvec<8>: eight
+ * mik_predict forms C = A_inv[:, :n] V (Mp x nf) on every device from that device's own copy of the inverse (k_cvec_fields<8>: eight
  * columns per read of A_inv; column f is bit for bit the c of a problem whose values are field f), kriges field 0 as the
  * values of the problem (mik_get_results / mik_take_results return field 0 and sigma^2) and the other fields from the
  * right-hand-side panel each launch has just written, eight per pass (k_rhs<0, 0, SP, false, 8>): no variogram is evaluated
@@ -371,7 +371,7 @@ int  mik_get_field_results(mik_handle *h, double *z_out);  /* nf x npt doubles, 
  * mik_set_fields and mik_set_problem clear them, and the values at the missing entries are replaced by 0.0 here (whatever they were).
  * With no gap set -- or a valid that is 1 everywhere -- every call behaves exactly as before.
  * For a field whose stations S (m of them) are missing and R = everything else (border and drift rows included), B = A^-1, b(p) the
- * right-hand side of point p, v0 the field with zeros at S and c0 = B[:, :n] v0 (k_cvec<8>), the block inverse gives
+ * right-hand side of point p, v0 the field with zeros at S and c0 = B[:, :n] v0 (k_cvec_fields<8>), the block inverse gives
  *     L L^T = B_SS,  W = L^-1 B[S, :],  g = L^-1 c0_S,  c~ = c0 - W^T g  (c~_S = 0),   z_R(p) = c~ . b(p),   sigma^2_R(p) = sigma^2(p) + |W b(p)|^2
  * -- exactly what a problem of the stations of R alone returns (same variogram, drift terms, exact_values), for any b_S.  mik_predict groups the
  * fields by identical valid column (a pattern without a gap does no work); per pattern one workgroup factors B[S, S] (mik_k_gaps.h on the fold
@@ -403,7 +403,7 @@ int  mik_predict_moving_window(mik_handle *h, int n_closest_points);
  *   n_closest_points = 0 (global form): from ALL other stations.  The kriging matrix has a zero diagonal, so with B = A^-1 and
  *     c = B[:, :n] v the block inverse gives  zhat_i = v_i - c_i / B_ii,  sigma^2_i = 1 / B_ii  -- for ordinary and universal kriging alike,
  *     drift and border rows included: all n predictions of all fields cost the factor, one pass over the station rows of the inverse
- *     (k_cvec<8> with a diagonal epilogue: plane f is bit for bit the one-field result) and one copy back.  Factors if no factor is resident
+ *     (k_cv_loo<8>, k_cvec_fields<8>'s sums with a diagonal epilogue: plane f is bit for bit the one-field result) and one copy back.  Factors if no factor is resident
  *     (a resident one is reused, like mik_predict); runs on the handle's own device (a device group's members take no part).  B_ii is used as
  *     computed: a zero or non-finite B_ii gives IEEE inf / nan in that entry, nothing is raised.  MIK_EINVAL with pseudo_inv: the identity
  *     needs a regular inverse.
@@ -416,9 +416,9 @@ int  mik_cross_validate(mik_handle *h, int n_closest_points /* 0 = global */, do
  * mik_problem); every group S is kriged from all stations outside it.  With B = A^-1, c = B[:, :n] v and R = everything else (border and drift
  * rows included) the block inverse gives  B_SS^-1 = A_SS - A_SR A_RR^-1 A_RS  and hence
  *     zhat_S = v_S - B_SS^-1 c_S,   sigma^2_S = diag(B_SS^-1)
- * exactly, for ordinary and universal kriging alike; a group of one station is mik_cross_validate's formula.  c is k_cvec<8>'s (leave-one-out's
+ * exactly, for ordinary and universal kriging alike; a group of one station is mik_cross_validate's formula.  c is k_cvec_fields<8>'s (leave-one-out's
  * sums); each group then costs one workgroup: gather B[S, S], Cholesky, triangular inverse, two triangular products per block of eight fields
- * (k_cvec<8, BIG>, mik_k_cvfolds.h: groups of up to 96 stations in LDS, larger ones in 64-column panels of m x m doubles of scratch).  Plane f
+ * (k_cv_folds<8, BIG>, mik_k_cvfolds.h: groups of up to 96 stations in LDS, larger ones in 64-column panels of m x m doubles of scratch).  Plane f
  * is bit for bit the one-field result, and a group's results depend on its members alone, not on its index.  A group whose block is not
  * numerically positive definite (non-positive or non-finite pivot) gets NaN in zhat and sigma^2; the others are unaffected, nothing is raised.
  * MIK_EINVAL: an index outside [0, nfolds), a group that holds every station, pseudo_inv.  Empty groups are allowed.  Otherwise the rules of
@@ -459,7 +459,7 @@ int  mik_predict_cov(mik_handle *h, double *cov_out /* npt x npt, row-major */);
  * without that matrix.  A nugget counts as variation of Z itself and averages down with nd.  Regional-linear drift rows take the mean of the
  * node coordinates, point_log rows the mean of the well term at the nodes (both on the device); the resident points' extra_rows, if any, are
  * taken as already averaged over the nodes by the caller.
- * On the device (mik_k_block.h) a further form of k_rhs writes bbar -- per station column a loop over the nodes, the offsets in LDS, nd
+ * On the device (mik_k_block.h) k_rhs_block, k_rhs with the nodes, writes bbar -- per station column a loop over the nodes, the offsets in LDS, nd
  * variogram values per station and block --, the dense contraction runs unchanged (always the dense path, also on a factor in Hilbert-curve
  * order: "sparse" reads 0 in mik_timing), one workgroup forms gbar once per call and a pass behind the reduce subtracts it.  nd = 1 with a zero offset is
  * mik_predict's dense result bit for bit; the results do not depend on how "chunk" cuts the call into launches.  Results come back through

@@ -1,6 +1,6 @@
 // mik_k_block.h -- block kriging (mik_predict_block): the estimate and the error variance of the arithmetic mean of Z over the nd
-// discretisation nodes of a block, from the one resident inverse.  Included by mik_predict.hip after mik_k_predict.h; the kernels are a
-// further form of k_rhs and further overloads of k_ss_reduce, no new names.
+// discretisation nodes of a block, from the one resident inverse.  Included by mik_predict.hip after mik_k_predict.h.  Kernels:
+// k_rhs_block (bbar), k_block_gamma (gbar), k_block_ss (sigma^2 - gbar).
 //
 // The resident points are the block centres (adjusted); node u of a block is centre + off[u], off the nd ADJUSTED offsets (T u, T =
 // stretch . rot: the adjustment is linear, so one table serves every block).  With b(.) the right-hand side exactly as k_rhs forms it at
@@ -12,11 +12,11 @@
 // which is the mean of the nd x nd block of mik_predict_cov's matrix on the nodes: the error variance of the mean of Z over the nodes
 // (a nugget is variation of Z itself and averages down with nd).
 //
-//   k_rhs<MODEL, NDIM>(BlockRhsArgs)        k_rhs's layout -- 8 blocks per workgroup, threads stride over j, point-major stores with
+//   k_rhs_block<MODEL, NDIM>                k_rhs's layout -- 8 blocks per workgroup, threads stride over j, point-major stores with
 //                                           ld = Mp, the z reduction at the end, lane for lane in k_rhs's order -- with the offsets in LDS
 //                                           and, per station column, a loop over the nodes.  nd = 1 (offset 0) is k_rhs bit for bit.
-//   k_ss_reduce<MODEL, NDIM>(BlockGammaArgs) one workgroup: gbar, once per call, in one fixed order
-//   k_ss_reduce(ss, nvalid, gbar)           s2_V = ss - gbar behind the unchanged dense reduce: per point, whatever launch the point is in
+//   k_block_gamma<MODEL, NDIM>              one workgroup: gbar, once per call, in one fixed order
+//   k_block_ss                              s2_V = ss - gbar behind the unchanged dense reduce: per point, whatever launch the point is in
 #pragma once
 #include "mik_k_predict.h"
 
@@ -31,7 +31,7 @@ struct BlockRhsArgs {
 };
 
 template <int MODEL, int NDIM>
-__global__ void __launch_bounds__(256) k_rhs(const BlockRhsArgs ba) {
+__global__ void __launch_bounds__(256) k_rhs_block(const BlockRhsArgs ba) {
   const RhsArgs& a = ba.r;
   const int nd = ba.nd;
   __shared__ double red[4][MIK_TP];
@@ -151,7 +151,7 @@ struct BlockGammaArgs {
 // One workgroup of 256 threads: thread t sums the pairs k = t, t + 256, ... (k = u nd + v) in ascending order, the 256 sums meet in a
 // binary tree, one division by nd^2.  Distances as the covariance's stage 0 forms them.
 template <int MODEL, int NDIM>
-__global__ void __launch_bounds__(256) k_ss_reduce(const BlockGammaArgs a) {
+__global__ void __launch_bounds__(256) k_block_gamma(const BlockGammaArgs a) {
   __shared__ double s[256];
   const long np = (long)a.nd * a.nd;
   double acc = 0.0;
@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(256) k_ss_reduce(const BlockGammaArgs a) {
 
 // sigma^2_V = ss - gbar behind the dense reduce of a launch (ss = -sum_iblk part[iblk][t], k_ss_reduce's): a pass of its own, per point,
 // whatever launch the point is in
-__global__ void __launch_bounds__(256) k_ss_reduce(double* __restrict__ ss, int nvalid, const double* __restrict__ gbar) {
+__global__ void __launch_bounds__(256) k_block_ss(double* __restrict__ ss, int nvalid, const double* __restrict__ gbar) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= nvalid) return;
   ss[t] = ss[t] - gbar[0];

@@ -1,5 +1,5 @@
 // mik_k_cov.h -- the kriging error covariance between the resident points (mik_predict_cov) from the one resident inverse.  Included by
-// mik_predict.hip after mik_k_predict.h; the kernels are further overloads of k_ss_reduce, no new names.
+// mik_predict.hip after mik_k_predict.h.  Kernels: k_cov_gamma (stage 0), k_cov_gemm (stages 1 and 2).
 //
 // b(p) the right-hand side of point p exactly as k_rhs writes it (drift rows, the border row and the exact_values zeroing included),
 // B = A^-1, e_p = Z(p) - z^(p).  Then
@@ -9,10 +9,10 @@
 // A range-aware predict (compact-support variogram on a Hilbert-ordered factor) runs as always, for the same reason -- its panels hold
 // delta on the candidate tiles only -- and Bt_all is written by one more dense k_rhs pass over the points (mik_predict.hip, predict_body).
 //
-//   stage 0   k_ss_reduce<MODEL, NDIM>(CovGammaArgs)   C[p][q] = -gamma*(d_pq) for p < q < P, elementwise from the adjusted coordinates
-//   stage 1   k_ss_reduce<NAI, 1>(CovGemmArgs)         Yt = Bt_all B^T (Pp x Mp, row-major): gemm_core(A = Bt_all rows, B = rows of B),
+//   stage 0   k_cov_gamma<MODEL, NDIM>                 C[p][q] = -gamma*(d_pq) for p < q < P, elementwise from the adjusted coordinates
+//   stage 1   k_cov_gemm<NAI, 1>                       Yt = Bt_all B^T (Pp x Mp, row-major): gemm_core(A = Bt_all rows, B = rows of B),
 //                                                      Yt[p][i] = sum_k b(p)_k B[i][k] = (B b(p))_i, a plain store
-//   stage 2   k_ss_reduce<NAI, 2>(CovGemmArgs)         the upper block triangle of 128 x 128 point tiles: acc = Bt_all[pblk] Yt[qblk]^T;
+//   stage 2   k_cov_gemm<NAI, 2>                       the upper block triangle of 128 x 128 point tiles: acc = Bt_all[pblk] Yt[qblk]^T;
 //                                                      for p < q (inside diagonal tiles too) C[p][q] - acc goes to [p][q] AND [q][p]:
 //                                                      every off-diagonal element is computed once and written twice, so C is exactly
 //                                                      symmetric; C[p][p] = the predict's sigma^2
@@ -20,7 +20,7 @@
 // j < Mp of every row t < palloc of a launch's panel -- zeros in the padding columns [M, Mp) and in the rows of the points that do not
 // exist [nvalid, palloc) (its `ok[q] ? val[q] : 0.0`).  Launches are equal multiples of 128 points and only the last one is short, so
 // the rows [P, Pp) of Bt_all are that launch's zero rows: finite, and their products are never stored (the epilogues stop at P).
-// Tiles are popped from k_contract's persistent per-XCD queues (super_tile_at), as k_ss_reduce<NAI>(GapGemmArgs) does; stage 2 walks the
+// Tiles are popped from k_contract's persistent per-XCD queues (pop_super_tile, mik_k_gaps.h), as k_gap_contract does; stage 2 walks the
 // square of point blocks and drops the tiles below the diagonal at the pop (a queue position costs one atomic and two barriers).
 // Every sum has one fixed order that depends on the point's place in the list alone, not on how the predict was cut into launches.
 #pragma once
@@ -39,7 +39,7 @@ struct CovGammaArgs {
 
 // blockIdx.x = p, blockIdx.y = 256 consecutive q; distances exactly as k_rhs forms them (point p in the place of the point, q of the station)
 template <int MODEL, int NDIM>
-__global__ void __launch_bounds__(256) k_ss_reduce(const CovGammaArgs a) {
+__global__ void __launch_bounds__(256) k_cov_gamma(const CovGammaArgs a) {
   const long p = blockIdx.x, q = (long)blockIdx.y * 256 + threadIdx.x;
   if (q <= p || q >= a.npt) return;
   double d, s2;
@@ -77,23 +77,16 @@ struct CovGemmArgs {
 // Accumulator acc[ai][bi][r] is row 16 ai + 4 r + (lane >> 4) of the wave's rows (wm * 16 NAI ..), column wn * 64 + 16 bi + (lane & 15)
 // of the block tile (gemm_core).
 template <int NAI, int STAGE>
-__global__ void __launch_bounds__(64 * 2 * (8 / NAI), 2 * (4 / NAI)) k_ss_reduce(const CovGemmArgs a) {
+__global__ void __launch_bounds__(64 * 2 * (8 / NAI), 2 * (4 / NAI)) k_cov_gemm(const CovGemmArgs a) {
   __shared__ GemmSmem sm;
-  unsigned xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  const int xcd = (int)(xcc & 7);
+  const int xcd = xcd_id();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave >> 1, wn = wave & 1, lq = lane >> 4, lc = lane & 15;
   const int nBblk = STAGE == 1 ? a.nIblk : a.nPblk;  // blocks of the B operand: rows of the inverse / point blocks of Yt
   int steal = 0;
   for (;;) {
     int ablk = 0, bblk = 0;
-    const int xq = (xcd + steal) & 7;
-    if (threadIdx.x == 0) sm.next = (long)__hip_atomic_fetch_add(&a.queue[xq], 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const long seq = sm.next;
-    const int kind = super_tile_at(a.nPblk, nBblk, xq, seq, ablk, bblk);
-    __syncthreads();  // everyone has read sm.next before it is written again
+    const int kind = pop_super_tile(a.queue, (xcd + steal) & 7, sm, a.nPblk, nBblk, ablk, bblk);
     if (kind == 2) {
       if (++steal == 8) return;
       continue;

@@ -1,5 +1,5 @@
 // mik_k_cvfolds.h -- leave-group-out cross-validation from the inverse (mik_cross_validate_folds).  Included by mik_k_predict.h after
-// mik_k_fields.h; the kernel is one more overload of k_cvec (k_cvec<FB, BIG>), no new kernel name.
+// mik_k_fields.h.  One kernel: k_cv_folds<FB, BIG>.
 //
 // A fold S of m stations, R everything else (border and drift rows included).  The kriging matrix has a zero diagonal on the station
 // rows, so with B = A^-1 and c = B[:, :N] v the block inverse gives  B_SS^-1 = A_SS - A_SR A_RR^-1 A_RS  and hence
@@ -27,7 +27,7 @@ namespace mik {
 struct CvfArgs {
   const double* B;    // the inverse, row stride ldb
   long ldb;
-  const double* C;    // c = B[:, :N] V: plane f at C + f n (k_cvec<FB>, coefficient overload)
+  const double* C;    // c = B[:, :N] V: plane f at C + f n (k_cvec_fields<FB>)
   const double* V;    // the fields, plane f at V + f n, zero planes up to a multiple of FB
   const int* idx;     // station positions (factor order) fold after fold, ascending inside a fold
   const long* desc;   // per workgroup of this launch: first entry of idx, m, first double of its block in scratch
@@ -300,7 +300,7 @@ __device__ __forceinline__ void cvf_apply(const CvfArgs& a, const double* W, lon
 
 // One workgroup per fold of the launch (a.desc: three longs per workgroup).  Dynamic LDS: BIG two 64 x 65 tiles, else m rows of a.ldw.
 template <int FB, bool BIG>
-__global__ void __launch_bounds__(256) k_cvec(const CvfArgs a) {
+__global__ void __launch_bounds__(256) k_cv_folds(const CvfArgs a) {
   extern __shared__ double cvf_lds[];
   const long* d = a.desc + 3 * (long)blockIdx.x;
   const long o0 = d[0];

@@ -1,19 +1,20 @@
 // mik_k_fields.h -- several value fields on one station set (mik_set_fields): the coefficient block C = A_inv[:, :N] V and the
 // z sums of the fields after the first, read back from the right-hand-side panel k_rhs has just written.
-// Included by mik_k_predict.h (after RhsArgs); the kernels are overloads of k_cvec and instantiations of k_rhs, no new names.
+// Included by mik_k_predict.h (after RhsArgs).  Kernels: k_cvec_fields (the coefficient block), k_cv_loo (leave-one-out); the z sums are
+// instantiations of k_rhs (rhs_fields below).
 #pragma once
 #include "mik_dev.h"
 
 namespace mik {
 
-#define MIK_FB 8  // fields per block of k_cvec<FB> and per read-back launch of k_rhs (FC): the columns of one block share each read of A_inv / B
+#define MIK_FB 8  // fields per block of k_cvec_fields<FB> and per read-back launch of k_rhs (FC): the columns of one block share each read of A_inv / B
 
 // C[f][i] = sum_{j<N} Ainv[i][j] * V[f][j] for the FB fields f0 .. f0 + FB - 1 of blockIdx.y (field-major V, ldv; C column stride ldc).
 // One wave per row, as k_cvec: every column is summed in k_cvec's order (lane j mod 64, then the xor butterfly), so column f is
 // bit for bit k_cvec of V[f]; the row of A_inv is read once for the FB columns.  V carries zero columns up to a multiple of FB.
 template <int FB>
-__global__ void __launch_bounds__(256) k_cvec(const double* __restrict__ Ainv, long ld, int M, int N, const double* __restrict__ V,
-                                              long ldv, double* __restrict__ C, long ldc, int Mp) {
+__global__ void __launch_bounds__(256) k_cvec_fields(const double* __restrict__ Ainv, long ld, int M, int N, const double* __restrict__ V,
+                                                     long ldv, double* __restrict__ C, long ldc, int Mp) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const long f0 = (long)blockIdx.y * FB;
@@ -41,12 +42,12 @@ __global__ void __launch_bounds__(256) k_cvec(const double* __restrict__ Ainv, l
 
 // Leave-one-out cross-validation from the inverse (mik_cross_validate, global form): the kriging matrix has a zero diagonal, so the block
 // inverse gives station i kriged from all the others as zhat_i = v_i - c_i / B_ii with sigma^2_i = 1 / B_ii, B = A_inv and c = B[:, :N] v --
-// ordinary and universal kriging alike (the drift and border rows belong to "the others").  The sums are the overload's above (same lanes,
+// ordinary and universal kriging alike (the drift and border rows belong to "the others").  The sums are k_cvec_fields's (same lanes,
 // same butterfly), so plane f is bit for bit the one-field result; the epilogue of a station row reads B[row][row] and V[f][row] and writes
 // zhat (plane stride ldz) and, from the first block of fields, 1 / B_ii.  B_ii is used as computed: zero or non-finite gives IEEE inf / nan.
 template <int FB>
-__global__ void __launch_bounds__(256) k_cvec(const double* __restrict__ Ainv, long ld, int N, const double* __restrict__ V, long ldv,
-                                              double* __restrict__ zhat, long ldz, double* __restrict__ ss) {
+__global__ void __launch_bounds__(256) k_cv_loo(const double* __restrict__ Ainv, long ld, int N, const double* __restrict__ V, long ldv,
+                                                double* __restrict__ zhat, long ldz, double* __restrict__ ss) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const long f0 = (long)blockIdx.y * FB;

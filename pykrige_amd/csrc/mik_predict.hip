@@ -46,56 +46,10 @@ int sort_points(mik_handle* h, long chunk, long nchunks) {
   return MIK_OK;
 }
 
-// V in fv: field f at fv + f N, in the caller's station order (want = 0: the moving window's too) or the factor's (1)
-int upload_fields(mik_handle* h, int want) {
-  // columns: a multiple of MIK_FB that also holds the last read-back launch's (fields 1 + MIK_FB k .. MIK_FB (k + 1), see launch_rhs)
-  const int nf = h->nf, nfp = ((nf - 1 + MIK_FB - 1) / MIK_FB) * MIK_FB + MIK_FB;
+// nf value fields on the host -- the fields of mik_set_fields, else (none set) the problem's own values -- as nfp planes of N with zero
+// planes from nf on; sorted: in the factor's station order (position i holds caller station sort_perm[i]), else the caller's
+static std::vector<double> stage_fields(const mik_handle* h, int nf, int nfp, bool sorted) {
   const long N = h->N;
-  if (h->fv_sorted != want) {
-    if (want && (long)h->sort_perm.size() != N) return fail(MIK_ESTATE, "mik_predict: station order of the factor unknown");
-    std::vector<double> v((size_t)nfp * (size_t)N, 0.0);
-    for (int f = 0; f < nf; ++f) {
-      const double* src = h->hfields.data() + (size_t)f * N;
-      double* dst = v.data() + (size_t)f * N;
-      if (want) {
-        for (long i = 0; i < N; ++i) dst[i] = src[h->sort_perm[(size_t)i]];
-      } else {
-        memcpy(dst, src, sizeof(double) * (size_t)N);
-      }
-    }
-    MIKC(h->fv.ensure(sizeof(double) * v.size()));
-    HIPC(hipMemcpyAsync(h->fv.p, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, h->stream));
-    HIPC(hipStreamSynchronize(h->stream));  // v is a local
-    h->fv_sorted = want;
-  }
-  return MIK_OK;
-}
-
-// Several value fields (mik_set_fields): C = A_inv[:, :N] V from this device's own copy of the inverse, MIK_FB columns per block of
-// k_cvec<MIK_FB> (column f is bit for bit the k_cvec of field f).  V goes up once per set of fields and station order.
-static int fields_coefficients(mik_handle* h) {
-  const int nf = h->nf, nfp = ((nf - 1 + MIK_FB - 1) / MIK_FB) * MIK_FB + MIK_FB;
-  const long N = h->N;
-  MIKC(upload_fields(h, h->factor_sorted ? 1 : 0));
-  MIKC(h->fc.ensure(sizeof(double) * (size_t)nfp * (size_t)h->Mp));
-  hipLaunchKernelGGL((k_cvec<MIK_FB>), dim3((h->Mp + 3) / 4, nfp / MIK_FB), dim3(256), 0, h->stream, (const double*)h->T.as<double>(),
-                     (long)h->Mp, h->M, h->N, (const double*)h->fv.as<double>(), (long)N, h->fc.as<double>(), (long)h->Mp, h->Mp);
-  HIPC(hipGetLastError());
-  return MIK_OK;
-}
-
-// Leave-one-out cross-validation from the resident inverse (mik_cross_validate, global form): one launch of the k_cvec<MIK_FB> overload with the
-// diagonal epilogue over the station rows -- the fields of mik_set_fields, else the problem's values, in the factor's station order -- then
-// one copy back and, for a factor in Hilbert-curve order, the un-permutation on the host.  Touches neither the resident points nor results.
-// zhat_out: max(nf, 1) planes of N in the caller's station order; ss_out: N.
-int one_cross_validate(mik_handle* h, double* zhat_out, double* ss_out) {
-  if (!h->have_factor) return fail(MIK_ESTATE, "mik_cross_validate: no factor");
-  if (h->pinv) return fail(MIK_EINVAL, "mik_cross_validate: the leave-one-out identity needs a regular inverse (pseudo_inv is set)");
-  HIPC(hipSetDevice(h->device));
-  const long N = h->N;
-  const int nf = std::max(h->nf, 1), nfp = ((nf + MIK_FB - 1) / MIK_FB) * MIK_FB;
-  const bool sorted = h->factor_sorted;
-  if (sorted && (long)h->sort_perm.size() != N) return fail(MIK_ESTATE, "mik_cross_validate: station order of the factor unknown");
   std::vector<double> v((size_t)nfp * (size_t)N, 0.0);
   for (int f = 0; f < nf; ++f) {
     const double* src = h->nf > 0 ? h->hfields.data() + (size_t)f * N : h->hvals.data();
@@ -106,15 +60,13 @@ int one_cross_validate(mik_handle* h, double* zhat_out, double* ss_out) {
       memcpy(dst, src, sizeof(double) * (size_t)N);
     }
   }
-  DevBuf dv, dout;  // V (padded to a multiple of MIK_FB fields); the zhat planes and 1 / B_ii behind them.  Freed after the stream drained
-  MIKC(dv.ensure(sizeof(double) * v.size()));
-  MIKC(dout.ensure(sizeof(double) * (size_t)(nfp + 1) * (size_t)N));
-  HIPC(hipMemcpyAsync(dv.p, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, h->stream));
-  double* zd = dout.as<double>();
-  double* sd = zd + (size_t)nfp * (size_t)N;
-  hipLaunchKernelGGL((k_cvec<MIK_FB>), dim3((unsigned)((N + 3) / 4), nfp / MIK_FB), dim3(256), 0, h->stream, (const double*)h->T.as<double>(),
-                     (long)h->Mp, (int)N, (const double*)dv.as<double>(), N, zd, N, sd);
-  HIPC(hipGetLastError());
+  return v;
+}
+
+// nf planes of zhat and sigma^2 behind them, from the device (zd, sd: planes of N in the factor's station order) to the caller's arrays in
+// the caller's station order; waits for the handle's stream
+static int cv_copy_back(mik_handle* h, const double* zd, const double* sd, int nf, bool sorted, double* zhat_out, double* ss_out) {
+  const long N = h->N;
   std::vector<double> out((size_t)(nf + 1) * (size_t)N);
   HIPC(hipMemcpyAsync(out.data(), zd, sizeof(double) * (size_t)nf * (size_t)N, hipMemcpyDeviceToHost, h->stream));
   HIPC(hipMemcpyAsync(out.data() + (size_t)nf * N, sd, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
@@ -131,12 +83,66 @@ int one_cross_validate(mik_handle* h, double* zhat_out, double* ss_out) {
   return MIK_OK;
 }
 
+// V in fv: field f at fv + f N, in the caller's station order (want = 0: the moving window's too) or the factor's (1)
+int upload_fields(mik_handle* h, int want) {
+  // columns: a multiple of MIK_FB that also holds the last read-back launch's (fields 1 + MIK_FB k .. MIK_FB (k + 1), see launch_rhs)
+  const int nf = h->nf, nfp = ((nf - 1 + MIK_FB - 1) / MIK_FB) * MIK_FB + MIK_FB;
+  const long N = h->N;
+  if (h->fv_sorted != want) {
+    if (want && (long)h->sort_perm.size() != N) return fail(MIK_ESTATE, "mik_predict: station order of the factor unknown");
+    const std::vector<double> v = stage_fields(h, nf, nfp, want != 0);
+    MIKC(h->fv.ensure(sizeof(double) * v.size()));
+    HIPC(hipMemcpyAsync(h->fv.p, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, h->stream));
+    HIPC(hipStreamSynchronize(h->stream));  // v is a local
+    h->fv_sorted = want;
+  }
+  return MIK_OK;
+}
+
+// Several value fields (mik_set_fields): C = A_inv[:, :N] V from this device's own copy of the inverse, MIK_FB columns per block of
+// k_cvec_fields<MIK_FB> (column f is bit for bit the k_cvec of field f).  V goes up once per set of fields and station order.
+static int fields_coefficients(mik_handle* h) {
+  const int nf = h->nf, nfp = ((nf - 1 + MIK_FB - 1) / MIK_FB) * MIK_FB + MIK_FB;
+  const long N = h->N;
+  MIKC(upload_fields(h, h->factor_sorted ? 1 : 0));
+  MIKC(h->fc.ensure(sizeof(double) * (size_t)nfp * (size_t)h->Mp));
+  hipLaunchKernelGGL((k_cvec_fields<MIK_FB>), dim3((h->Mp + 3) / 4, nfp / MIK_FB), dim3(256), 0, h->stream, (const double*)h->T.as<double>(),
+                     (long)h->Mp, h->M, h->N, (const double*)h->fv.as<double>(), (long)N, h->fc.as<double>(), (long)h->Mp, h->Mp);
+  HIPC(hipGetLastError());
+  return MIK_OK;
+}
+
+// Leave-one-out cross-validation from the resident inverse (mik_cross_validate, global form): one launch of k_cv_loo<MIK_FB> (k_cvec_fields's sums with a
+// diagonal epilogue) over the station rows -- the fields of mik_set_fields, else the problem's values, in the factor's station order -- then
+// one copy back and, for a factor in Hilbert-curve order, the un-permutation on the host.  Touches neither the resident points nor results.
+// zhat_out: max(nf, 1) planes of N in the caller's station order; ss_out: N.
+int one_cross_validate(mik_handle* h, double* zhat_out, double* ss_out) {
+  if (!h->have_factor) return fail(MIK_ESTATE, "mik_cross_validate: no factor");
+  if (h->pinv) return fail(MIK_EINVAL, "mik_cross_validate: the leave-one-out identity needs a regular inverse (pseudo_inv is set)");
+  HIPC(hipSetDevice(h->device));
+  const long N = h->N;
+  const int nf = std::max(h->nf, 1), nfp = ((nf + MIK_FB - 1) / MIK_FB) * MIK_FB;
+  const bool sorted = h->factor_sorted;
+  if (sorted && (long)h->sort_perm.size() != N) return fail(MIK_ESTATE, "mik_cross_validate: station order of the factor unknown");
+  const std::vector<double> v = stage_fields(h, nf, nfp, sorted);
+  DevBuf dv, dout;  // V (padded to a multiple of MIK_FB fields); the zhat planes and 1 / B_ii behind them.  Freed after the stream drained
+  MIKC(dv.ensure(sizeof(double) * v.size()));
+  MIKC(dout.ensure(sizeof(double) * (size_t)(nfp + 1) * (size_t)N));
+  HIPC(hipMemcpyAsync(dv.p, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, h->stream));
+  double* zd = dout.as<double>();
+  double* sd = zd + (size_t)nfp * (size_t)N;
+  hipLaunchKernelGGL((k_cv_loo<MIK_FB>), dim3((unsigned)((N + 3) / 4), nfp / MIK_FB), dim3(256), 0, h->stream, (const double*)h->T.as<double>(),
+                     (long)h->Mp, (int)N, (const double*)dv.as<double>(), N, zd, N, sd);
+  HIPC(hipGetLastError());
+  return cv_copy_back(h, zd, sd, nf, sorted, zhat_out, ss_out);
+}
+
 // Leave-group-out cross-validation from the resident inverse (mik_cross_validate_folds): fold[i] in [0, nfolds) is the group of caller
 // station i; every group is kriged from all the others (mik_k_cvfolds.h).  The per-fold station lists are built in the FACTOR's station
 // order (a Hilbert-ordered factor holds caller station sort_perm[p] at position p), ascending, so that a fold's sums depend on its members
-// alone.  c = B[:, :N] V by the coefficient overload of k_cvec<MIK_FB> (leave-one-out's sums), then one launch per size class: folds of
+// alone.  c = B[:, :N] V by k_cvec_fields<MIK_FB> (leave-one-out's sums), then one launch of k_cv_folds per size class: folds of
 // up to MIK_CVF_LDS stations factor their block in LDS, larger ones in m x m doubles of scratch (sum of m^2 over those folds, at most N^2,
-// one allocation with the two work planes, freed after the stream drained).  Copy back and un-permutation as one_cross_validate.
+// one allocation with the two work planes, freed after the stream drained).  Copy back and un-permutation as one_cross_validate (cv_copy_back).
 int one_cross_validate_folds(mik_handle* h, const int32_t* fold, int nfolds, double* zhat_out, double* ss_out) {
   if (!h->have_factor) return fail(MIK_ESTATE, "mik_cross_validate_folds: no factor");
   if (h->pinv) return fail(MIK_EINVAL, "mik_cross_validate_folds: the block-inverse identity needs a regular inverse (pseudo_inv is set)");
@@ -176,16 +182,7 @@ int one_cross_validate_folds(mik_handle* h, const int32_t* fold, int nfolds, dou
         ++nsmall;
       }
     }
-  std::vector<double> v((size_t)nfp * (size_t)N, 0.0);
-  for (int f = 0; f < nf; ++f) {
-    const double* src = h->nf > 0 ? h->hfields.data() + (size_t)f * N : h->hvals.data();
-    double* dst = v.data() + (size_t)f * N;
-    if (sorted) {
-      for (long i = 0; i < N; ++i) dst[i] = src[h->sort_perm[(size_t)i]];
-    } else {
-      memcpy(dst, src, sizeof(double) * (size_t)N);
-    }
-  }
+  const std::vector<double> v = stage_fields(h, nf, nfp, sorted);
   // V and c (nfp planes each); zhat (nfp planes) and sigma^2; scratch and the two work planes; the lists.  Freed after the stream drained
   DevBuf dv, dout, dwork, dlist;
   MIKC(dv.ensure(sizeof(double) * 2 * v.size()));
@@ -197,7 +194,7 @@ int one_cross_validate_folds(mik_handle* h, const int32_t* fold, int nfolds, dou
   int* didx = reinterpret_cast<int*>(dlist.as<long>() + desc.size());
   HIPC(hipMemcpyAsync(didx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice, h->stream));
   double* cd = dv.as<double>() + v.size();
-  hipLaunchKernelGGL((k_cvec<MIK_FB>), dim3((unsigned)((N + 3) / 4), nfp / MIK_FB), dim3(256), 0, h->stream, (const double*)h->T.as<double>(),
+  hipLaunchKernelGGL((k_cvec_fields<MIK_FB>), dim3((unsigned)((N + 3) / 4), nfp / MIK_FB), dim3(256), 0, h->stream, (const double*)h->T.as<double>(),
                      (long)h->Mp, (int)N, (int)N, (const double*)dv.as<double>(), N, cd, N, (int)N);
   CvfArgs a;
   a.B = h->T.as<double>(), a.ldb = h->Mp, a.C = cd, a.V = dv.as<double>(), a.idx = didx, a.desc = dlist.as<long>();
@@ -205,30 +202,17 @@ int one_cross_validate_folds(mik_handle* h, const int32_t* fold, int nfolds, dou
   a.zhat = dout.as<double>(), a.ss = a.zhat + (size_t)nfp * (size_t)N, a.n = N, a.nfb = nfp / MIK_FB, a.ldw = msmall | 1;
   if (nsmall) {
     const size_t lds = sizeof(double) * (size_t)msmall * (size_t)a.ldw;
-    HIPC(hipFuncSetAttribute((const void*)k_cvec<MIK_FB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_cvec<MIK_FB, false>), dim3((unsigned)nsmall), dim3(256), lds, h->stream, a);
+    HIPC(hipFuncSetAttribute((const void*)k_cv_folds<MIK_FB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_cv_folds<MIK_FB, false>), dim3((unsigned)nsmall), dim3(256), lds, h->stream, a);
   }
   if (nbig) {
     const size_t lds = sizeof(double) * 2 * MIK_CVF_NB * MIK_CVF_TLD;
     a.desc += 3 * (size_t)nsmall;
-    HIPC(hipFuncSetAttribute((const void*)k_cvec<MIK_FB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_cvec<MIK_FB, true>), dim3((unsigned)nbig), dim3(256), lds, h->stream, a);
+    HIPC(hipFuncSetAttribute((const void*)k_cv_folds<MIK_FB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_cv_folds<MIK_FB, true>), dim3((unsigned)nbig), dim3(256), lds, h->stream, a);
   }
   HIPC(hipGetLastError());
-  std::vector<double> out((size_t)(nf + 1) * (size_t)N);
-  HIPC(hipMemcpyAsync(out.data(), a.zhat, sizeof(double) * (size_t)nf * (size_t)N, hipMemcpyDeviceToHost, h->stream));
-  HIPC(hipMemcpyAsync(out.data() + (size_t)nf * N, a.ss, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
-  HIPC(hipStreamSynchronize(h->stream));
-  for (int f = 0; f <= nf; ++f) {
-    const double* src = out.data() + (size_t)f * N;
-    double* dst = f < nf ? zhat_out + (size_t)f * N : ss_out;
-    if (sorted) {
-      for (long i = 0; i < N; ++i) dst[h->sort_perm[(size_t)i]] = src[i];
-    } else {
-      memcpy(dst, src, sizeof(double) * (size_t)N);
-    }
-  }
-  return MIK_OK;
+  return cv_copy_back(h, a.zhat, a.ss, nf, sorted, zhat_out, ss_out);
 }
 
 // point blocks per group of k_sp_tiles_g's queue order (a group's tiles run on one XCD, tile position ascending, point block fast;
@@ -343,14 +327,11 @@ static int plan_predict(mik_handle* h, Plan& p, bool cov) {
   return MIK_OK;
 }
 
-// the right-hand sides of launch l into lane ln's panel on stream st, with z of every field; the range-aware path first marks the
-// candidate station tiles of every point block and then writes delta for those only
-// zscratch (a dense plan only): a pass that is there for its panel alone -- z goes to zscratch, no event is recorded
-static int launch_rhs(mik_handle* h, const Plan& p, const Launch& l, PredictLane& ln, hipStream_t st, double* zscratch = nullptr) {
-  const LaunchEvents& ev = h->pr_launch[(size_t)l.c];
-  const long t0 = l.t0, npt = p.npt;
+// what every right-hand-side kernel of launch l is told about the problem and the launch's points; the panel Bt, the coefficients cvec
+// and the place zout of z are the caller's, and what only the range-aware path and the fields' read-back read stays zero
+static RhsArgs rhs_args(mik_handle* h, const Plan& p, const Launch& l) {
+  const long t0 = l.t0;
   RhsArgs a{};
-  a.Bt = p.panel ? p.panel + (size_t)t0 * (size_t)p.Mp : ln.Bt.as<double>();
   a.ld = p.Mp;
   a.palloc = l.palloc;
   a.nvalid = l.nvalid;
@@ -374,7 +355,18 @@ static int launch_rhs(mik_handle* h, const Plan& p, const Launch& l, PredictLane
   a.nextra = h->nextra;
   a.wells = h->wells.as<double>();
   a.extra = h->nextra ? h->extra_rows.as<double>() + t0 : nullptr;
-  a.extra_stride = npt;
+  a.extra_stride = p.npt;
+  return a;
+}
+
+// the right-hand sides of launch l into lane ln's panel on stream st, with z of every field; the range-aware path first marks the
+// candidate station tiles of every point block and then writes delta for those only
+// zscratch (a dense plan only): a pass that is there for its panel alone -- z goes to zscratch, no event is recorded
+static int launch_rhs(mik_handle* h, const Plan& p, const Launch& l, PredictLane& ln, hipStream_t st, double* zscratch = nullptr) {
+  const LaunchEvents& ev = h->pr_launch[(size_t)l.c];
+  const long t0 = l.t0, npt = p.npt;
+  RhsArgs a = rhs_args(h, p, l);
+  a.Bt = p.panel ? p.panel + (size_t)t0 * (size_t)p.Mp : ln.Bt.as<double>();
   a.cvec = p.nf > 0 ? (const double*)h->fc.as<double>() : (const double*)h->cvec.as<double>();
   a.zout = (zscratch ? zscratch : h->z.as<double>()) + t0;
   const dim3 grid(l.palloc / MIK_TP), block(256);
@@ -470,11 +462,11 @@ static int contract_dense(mik_handle* h, const Plan& p, const Launch& l) {
     g.W = h->gap_W.as<double>(), g.ldw = ldm, g.Bt = Bi, g.ldb = ldm, g.part = h->gap_part.as<double>();
     g.palloc = l.palloc, g.nRblk = p.gap_nRblk, g.kend = kend, g.queue = qp;
     const unsigned ggrid = (unsigned)std::min<long>(2L * h->n_cu, super_grid(p.gap_nRblk, l.nTb));
-    hipLaunchKernelGGL((k_ss_reduce<2>), dim3(ggrid), dim3(512), 0, sc, g);
+    hipLaunchKernelGGL((k_gap_contract<2>), dim3(ggrid), dim3(512), 0, sc, g);
     GapRedArgs r{};
     r.part = g.part, r.palloc = l.palloc, r.nvalid = l.nvalid, r.ss = h->ss.as<double>() + l.t0, r.desc = p.gap_desc;
     r.out = h->gap_ss.as<double>() + l.t0, r.ldo = p.npt;
-    hipLaunchKernelGGL(k_ss_reduce, dim3((l.nvalid + 255) / 256, p.gap_np), dim3(256), 0, sc, r);
+    hipLaunchKernelGGL(k_gap_ss, dim3((l.nvalid + 255) / 256, p.gap_np), dim3(256), 0, sc, r);
   }
   return MIK_OK;
 }
@@ -592,22 +584,20 @@ static int gaps_setup(mik_handle* h, Plan& p) {
     HIPC(hipMemsetAsync(a.W + (size_t)16 * ngroups * Mp, 0, sizeof(double) * (size_t)(rowsp - 16L * ngroups) * Mp, st));
   if (nsmall) {
     const size_t lds = sizeof(double) * (size_t)msmall * (size_t)a.ldw;
-    void (*kf)(GapArgs) = k_cvec<0>;  // (the overload with this argument)
-    HIPC(hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_cvec<0>), dim3((unsigned)nsmall), dim3(256), lds, st, a);
+    HIPC(hipFuncSetAttribute((const void*)k_gap_factor<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_gap_factor<false>), dim3((unsigned)nsmall), dim3(256), lds, st, a);
   }
   if (np > nsmall) {
     const size_t lds = sizeof(double) * 2 * MIK_CVF_NB * MIK_CVF_TLD;
     GapArgs b = a;
     b.desc += (size_t)MIK_GAP_DESC * nsmall;
-    void (*kf)(GapArgs) = k_cvec<1>;
-    HIPC(hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_cvec<1>), dim3((unsigned)(np - nsmall)), dim3(256), lds, st, b);
+    HIPC(hipFuncSetAttribute((const void*)k_gap_factor<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_gap_factor<true>), dim3((unsigned)(np - nsmall)), dim3(256), lds, st, b);
   }
   const unsigned ncb = (unsigned)((Mp + 255) / 256);
-  hipLaunchKernelGGL((k_cvec<2>), dim3(ncb, (unsigned)ngroups), dim3(256), 0, st, a);
-  hipLaunchKernelGGL((k_cvec<3>), dim3((unsigned)nq), dim3(256), 0, st, a);
-  hipLaunchKernelGGL((k_cvec<4>), dim3(ncb, (unsigned)nq), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_gap_w, dim3(ncb, (unsigned)ngroups), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_gap_g, dim3((unsigned)nq), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_gap_coef, dim3(ncb, (unsigned)nq), dim3(256), 0, st, a);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(st));  // blob is a local
   return MIK_OK;
@@ -834,16 +824,16 @@ static int cov_stages(mik_handle* h, const Plan& p, long Pp, double* Yt, double*
   g.px = h->px.as<double>(), g.py = h->py.as<double>(), g.pz = h->ndim == 3 ? h->pz.as<double>() : nullptr;
   g.npt = P, g.v = h->v, g.eps = h->eps, g.C = C, g.ldc = Pp;
   const dim3 ggrid((unsigned)P, (unsigned)((P + 255) / 256)), gblock(256);
-  DISPATCH_MODEL_NDIM(h->model, h->geo ? 1 : h->ndim, k_ss_reduce, ggrid, gblock, st, g);
+  DISPATCH_MODEL_NDIM(h->model, h->geo ? 1 : h->ndim, k_cov_gamma, ggrid, gblock, st, g);
   HIPC(hipEventRecord(h->ev_cov[1], st));
   CovGemmArgs a{};
   a.Bt = p.panel, a.T = h->T.as<double>(), a.Yt = Yt, a.ld = p.Mp, a.C = C, a.ldc = Pp, a.ss = h->ss.as<double>(), a.npt = P;
   a.nPblk = nPblk, a.nIblk = p.nIblk, a.kend = p.kend, a.queue = ln.queue.as<unsigned long long>();
   HIPC(hipMemsetAsync(ln.queue.p, 0, 8 * sizeof(unsigned long long), st));
-  hipLaunchKernelGGL((k_ss_reduce<2, 1>), dim3((unsigned)std::min<long>(2L * h->n_cu, super_grid(nPblk, p.nIblk))), dim3(512), 0, st, a);
+  hipLaunchKernelGGL((k_cov_gemm<2, 1>), dim3((unsigned)std::min<long>(2L * h->n_cu, super_grid(nPblk, p.nIblk))), dim3(512), 0, st, a);
   HIPC(hipEventRecord(h->ev_cov[2], st));
   HIPC(hipMemsetAsync(ln.queue.p, 0, 8 * sizeof(unsigned long long), st));
-  hipLaunchKernelGGL((k_ss_reduce<2, 2>), dim3((unsigned)std::min<long>(2L * h->n_cu, super_grid(nPblk, nPblk))), dim3(512), 0, st, a);
+  hipLaunchKernelGGL((k_cov_gemm<2, 2>), dim3((unsigned)std::min<long>(2L * h->n_cu, super_grid(nPblk, nPblk))), dim3(512), 0, st, a);
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(h->ev_cov[3], st));
   const long rb = std::min<long>(Pp, std::max<long>(128, (((32L << 20) / (8 * P)) / 128) * 128));  // rows per piece
@@ -876,10 +866,11 @@ static int cov_stages(mik_handle* h, const Plan& p, long Pp, double* Yt, double*
   return MIK_OK;
 }
 
-// cov_out != nullptr: the predict with the error covariance (one_predict_cov; mik_k_cov.h)
-static int predict_body(mik_handle* h, double* cov_out) {
-  if (!h || !h->have_factor) return fail(MIK_ESTATE, "mik_predict: factor first");
-  if (!h->have_points) return fail(MIK_ESTATE, "mik_predict: set points first");
+// What a predict of the resident points starts with (who: the entry point, for the messages): the state checks, the device, the timing
+// fields of a fresh run, no planes of gappy fields.  *empty: there are no points -- the (empty) results are there and the caller returns.
+static int predict_prologue(mik_handle* h, const char* who, bool* empty) {
+  if (!h || !h->have_factor) return fail(MIK_ESTATE, std::string(who) + ": factor first");
+  if (!h->have_points) return fail(MIK_ESTATE, std::string(who) + ": set points first");
   HIPC(hipSetDevice(h->device));
   h->tm.rhs_ms = h->tm.contract_ms = h->tm.predict_ms = 0.0;
   h->tm.contract_launches = 0;
@@ -889,10 +880,16 @@ static int predict_body(mik_handle* h, double* cov_out) {
   h->tm.mw_kernel = 0;
   h->nf_done = h->nf;
   h->gap_plane.clear();
-  if (h->npt == 0) {
-    h->have_results = true;
-    return MIK_OK;
-  }
+  *empty = h->npt == 0;
+  if (*empty) h->have_results = true;
+  return MIK_OK;
+}
+
+// cov_out != nullptr: the predict with the error covariance (one_predict_cov; mik_k_cov.h)
+static int predict_body(mik_handle* h, double* cov_out) {
+  bool empty = false;
+  MIKC(predict_prologue(h, "mik_predict", &empty));
+  if (empty) return MIK_OK;
   Plan p{};
   MIKC(plan_predict(h, p, cov_out != nullptr));
   const long Pp = ((h->npt + 127) / 128) * 128;
@@ -958,7 +955,7 @@ int one_predict_cov(mik_handle* h, double* cov_out) { return predict_body(h, cov
 // it are the block's.
 #include "mik_k_block.h"
 
-// the six named models x NDIM 2 / 3 -- no geographic form, no custom variogram
+// the six named models x NDIM 2 / 3 -- no geographic form, no custom variogram (DISPATCH_MODEL_NDIM would instantiate those as well)
 #define DISPATCH_BLOCK_NDIM(model, NDIM, KERNEL, grid, block, stream, args)                          \
   switch (model) {                                                                                   \
     case 0: hipLaunchKernelGGL((KERNEL<0, NDIM>), grid, block, 0, stream, args); break;              \
@@ -981,58 +978,23 @@ static int launch_rhs_block(mik_handle* h, const Plan& p, const Launch& l, const
   hipStream_t st = h->stream;
   BlockRhsArgs ba{};
   RhsArgs& a = ba.r;
+  a = rhs_args(h, p, l);
   a.Bt = h->lane[0].Bt.as<double>();
-  a.ld = p.Mp;
-  a.palloc = l.palloc;
-  a.nvalid = l.nvalid;
-  a.px = h->px.as<double>() + t0;
-  a.py = h->py.as<double>() + t0;
-  a.pz = h->ndim == 3 ? h->pz.as<double>() + t0 : nullptr;
-  a.N = h->N;
-  a.p = h->p;
-  a.M = h->M;
-  a.Mp = p.Mp;
-  a.ndim = h->ndim;
-  a.xs = h->factor_sorted ? h->xs_s.as<double>() : h->xs.as<double>();
-  a.ys = h->factor_sorted ? h->ys_s.as<double>() : h->ys.as<double>();
-  a.zs = h->factor_sorted ? h->zs_s.as<double>() : h->zs.as<double>();
-  a.dsc = h->factor_eq ? h->dsc.as<double>() : nullptr;
-  a.v = h->v;
-  a.exact = h->exact;
-  a.eps = h->eps;
-  a.rl = h->rl;
-  a.nwells = h->nwells;
-  a.nextra = h->nextra;
-  a.wells = h->wells.as<double>();
-  a.extra = h->nextra ? h->extra_rows.as<double>() + t0 : nullptr;
-  a.extra_stride = p.npt;
-  a.cvec = h->cvec.as<double>();
+  a.cvec = h->cvec.as<double>();  // (no fields; no candidate tiles and no point order: the dense path)
   a.zout = h->z.as<double>() + t0;
   ba.off = off, ba.nd = nd;
   const dim3 grid(l.palloc / MIK_TP), block(256);
   HIPC(hipEventRecord(ev.rhs_begin, st));
-  DISPATCH_BLOCK(h->model, h->ndim, k_rhs, grid, block, st, ba);
+  DISPATCH_BLOCK(h->model, h->ndim, k_rhs_block, grid, block, st, ba);
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(ev.rhs_end, st));
   return MIK_OK;
 }
 
 int one_predict_block(mik_handle* h, const double* offsets, int nd) {
-  if (!h || !h->have_factor) return fail(MIK_ESTATE, "mik_predict_block: factor first");
-  if (!h->have_points) return fail(MIK_ESTATE, "mik_predict_block: set points first");
-  HIPC(hipSetDevice(h->device));
-  h->tm.rhs_ms = h->tm.contract_ms = h->tm.predict_ms = 0.0;
-  h->tm.contract_launches = 0;
-  h->tm.contract_flops_executed = 0.0;
-  h->tm.symmetric = h->opt_sym;
-  h->tm.engine = 0;
-  h->tm.mw_kernel = 0;
-  h->nf_done = h->nf;
-  h->gap_plane.clear();
-  if (h->npt == 0) {
-    h->have_results = true;
-    return MIK_OK;
-  }
+  bool empty = false;
+  MIKC(predict_prologue(h, "mik_predict_block", &empty));
+  if (empty) return MIK_OK;
   Plan p{};
   MIKC(plan_predict(h, p, false));
   // always the dense path, also on a factor in Hilbert-curve order (as the gaps predict): sigma^2 = 2 s - delta^T A_inv delta is an
@@ -1051,13 +1013,13 @@ int one_predict_block(mik_handle* h, const double* offsets, int nd) {
   {  // gbar does not depend on the block: once per call, one workgroup
     BlockGammaArgs g{};
     g.off = off, g.nd = nd, g.v = h->v, g.eps = h->eps, g.gbar = gbar;
-    DISPATCH_BLOCK(h->model, h->ndim, k_ss_reduce, dim3(1), dim3(256), h->stream, g);
+    DISPATCH_BLOCK(h->model, h->ndim, k_block_gamma, dim3(1), dim3(256), h->stream, g);
   }
   for (long c = 0; c < p.nchunks; ++c) {
     const Launch l(p, c);
     MIKC(launch_rhs_block(h, p, l, off, nd));
     MIKC(contract_dense(h, p, l));
-    hipLaunchKernelGGL(k_ss_reduce, dim3((l.nvalid + 255) / 256), dim3(256), 0, h->stream, h->ss.as<double>() + l.t0, l.nvalid, (const double*)gbar);
+    hipLaunchKernelGGL(k_block_ss, dim3((l.nvalid + 255) / 256), dim3(256), 0, h->stream, h->ss.as<double>() + l.t0, l.nvalid, (const double*)gbar);
     MIKC(copy_out(h, p, l, h->stream));
   }
   HIPC(hipGetLastError());

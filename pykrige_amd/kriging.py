@@ -778,6 +778,41 @@ class _KrigingBase:
             zf = np.ma.array(zf, mask=np.zeros(zf.shape, dtype=bool))
         return zf.reshape((nf,) + tuple(shape)), ss
 
+    # ---------------------------------------------------------------- what execute_cov and execute_block share
+    def _grid_or_points(self, style, backend, masked_message):
+        if style == "masked":
+            raise ValueError(masked_message)
+        if style != "grid" and style != "points":
+            raise ValueError("style argument must be 'grid' or 'points'")
+        self._check_backend(backend, None)
+
+    def _refuse_custom_and_pinv(self, name, custom_why, pinv_why):
+        if self.variogram_model == "custom":
+            raise NotImplementedError("%s: variogram_model='custom' is evaluated on the host; %s" % (name, custom_why))
+        if self.pseudo_inv:
+            raise ValueError("%s needs a regular inverse: %s for pseudo_inv=True" % (name, pinv_why))
+
+    @staticmethod
+    def _refuse_group(h, name, one_device):
+        if h is not None and h.n_devices > 1:
+            raise ValueError("%s: this object's handle spans a device group of %d devices; %s" % (name, h.n_devices, one_device))
+
+    def _resident_problem(self, P, name, one_device):
+        """The handle with this object's problem set (only if its key changed) and the points P loaded: (handle, factor key).
+        _upload_and_factor without its factor(): mik_predict_cov / mik_predict_block refuse (an oversized P among the reasons) before
+        they launch anything and factor themselves if no factor is resident."""
+        h = self._get_handle()
+        self._refuse_group(h, name, one_device)
+        key = self._problem_key()
+        if key is not None:
+            key = (key, h.option_epoch)
+        self.factor_reused = key is not None and key == getattr(self, "_factor_key", None)
+        if not self.factor_reused:
+            self._set_problem(h)
+        self._max_points = max(self._max_points, P.npt)
+        P.load(h, self._ndim)
+        return h, key
+
     # ---------------------------------------------------------------- error covariance between prediction points (mik_predict_cov)
     _COV_DOC = """Kriged values and the kriging error covariance between the prediction points.
 
@@ -808,37 +843,15 @@ class _KrigingBase:
 
     def _execute_cov(self, style, axes, backend, specified_drift_arrays, universal):
         """execute_cov of the four classes: every argument is checked on the host before the device is touched."""
-        if style == "masked":
-            raise ValueError("execute_cov: style 'masked' has no covariance matrix; pass the unmasked points as style 'points'")
-        if style != "grid" and style != "points":
-            raise ValueError("style argument must be 'grid' or 'points'")
-        self._check_backend(backend, None)
+        self._grid_or_points(style, backend, "execute_cov: style 'masked' has no covariance matrix; pass the unmasked points as style 'points'")
         if not universal and specified_drift_arrays is not None:
             raise ValueError("execute_cov: specified_drift_arrays belongs to the universal-kriging classes")
-        if self.variogram_model == "custom":
-            raise NotImplementedError("execute_cov: variogram_model='custom' is evaluated on the host; the covariance between points is not built for it")
-        if self.pseudo_inv:
-            raise ValueError("execute_cov needs a regular inverse: the covariance identity does not hold for pseudo_inv=True")
-        if self._handle is not None and self._handle.n_devices > 1:
-            raise ValueError("execute_cov: this object's handle spans a device group of %d devices; the covariance is computed on one "
-                             "device" % self._handle.n_devices)
+        self._refuse_custom_and_pinv("execute_cov", "the covariance between points is not built for it", "the covariance identity does not hold")
+        self._refuse_group(self._handle, "execute_cov", "the covariance is computed on one device")
         P = self._prepare(style, axes, None, **(dict(specified_drift_arrays=specified_drift_arrays, backend=backend) if universal else {}))
         if P.npt == 0:
             raise ValueError("execute_cov: no points")
-        # _upload_and_factor without its factor(): mik_predict_cov refuses (an oversized P among the reasons) before it launches anything
-        # and factors itself if no factor is resident
-        h = self._get_handle()
-        if h.n_devices > 1:
-            raise ValueError("execute_cov: this object's handle spans a device group of %d devices; the covariance is computed on one "
-                             "device" % h.n_devices)
-        key = self._problem_key()
-        if key is not None:
-            key = (key, h.option_epoch)
-        self.factor_reused = key is not None and key == getattr(self, "_factor_key", None)
-        if not self.factor_reused:
-            self._set_problem(h)
-        self._max_points = max(self._max_points, P.npt)
-        P.load(h, self._ndim)
+        h, key = self._resident_problem(P, "execute_cov", "the covariance is computed on one device")
         cov = h.predict_cov()
         self._factor_key = key
         self.last_timing = h.timing()
@@ -882,23 +895,14 @@ class _KrigingBase:
 
     def _execute_block(self, style, axes, block_size, n_disc, backend):
         """execute_block of the four classes: every argument is checked on the host before the device is touched."""
-        if style == "masked":
-            raise ValueError("execute_block: style 'masked' is not built; pass the unmasked block centres as style 'points'")
-        if style != "grid" and style != "points":
-            raise ValueError("style argument must be 'grid' or 'points'")
-        self._check_backend(backend, None)
+        self._grid_or_points(style, backend, "execute_block: style 'masked' is not built; pass the unmasked block centres as style 'points'")
         off = core.block_node_offsets(self._ndim, block_size, n_disc)
         if getattr(self, "coordinates_type", "euclidean") == "geographic":
             raise ValueError("execute_block: coordinates_type='geographic' is not built (the blocks of a lon / lat grid are not congruent)")
-        if self.variogram_model == "custom":
-            raise NotImplementedError("execute_block: variogram_model='custom' is evaluated on the host; block kriging is not built for it")
-        if self.pseudo_inv:
-            raise ValueError("execute_block needs a regular inverse: the block variance is not defined for pseudo_inv=True")
+        self._refuse_custom_and_pinv("execute_block", "block kriging is not built for it", "the block variance is not defined")
         if getattr(self, "external_Z_drift", False) or getattr(self, "specified_drift", False):
             raise NotImplementedError("execute_block: external_Z and specified drifts are given point by point; their block averages are not built")
-        if self._handle is not None and self._handle.n_devices > 1:
-            raise ValueError("execute_block: this object's handle spans a device group of %d devices; blocks are kriged on one device"
-                             % self._handle.n_devices)
+        self._refuse_group(self._handle, "execute_block", "blocks are kriged on one device")
         off = core.adjust_offsets(off, self._ndim, self._scaling(), self._angle())
         P = self._prepare(style, axes, None)
         if getattr(self, "functional_drift", False) and P.npt:
@@ -912,19 +916,7 @@ class _KrigingBase:
                     acc = v if acc is None else acc + v
                 rows.append(acc / float(off.shape[0]))
             P.extra = np.array(rows, dtype=np.float64)
-        # as _execute_cov: mik_predict_block refuses before it launches anything and factors itself if no factor is resident
-        h = self._get_handle()
-        if h.n_devices > 1:
-            raise ValueError("execute_block: this object's handle spans a device group of %d devices; blocks are kriged on one device"
-                             % h.n_devices)
-        key = self._problem_key()
-        if key is not None:
-            key = (key, h.option_epoch)
-        self.factor_reused = key is not None and key == getattr(self, "_factor_key", None)
-        if not self.factor_reused:
-            self._set_problem(h)
-        self._max_points = max(self._max_points, P.npt)
-        P.load(h, self._ndim)
+        h, key = self._resident_problem(P, "execute_block", "blocks are kriged on one device")
         h.predict_block(off)
         self._factor_key = key
         self.last_timing = h.timing()

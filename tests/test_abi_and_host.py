@@ -58,7 +58,7 @@ REACHABLE = {
     "k_diag_inv_b": "sweep: blocked diagonal-block inverse", "k_panel": "sweep: column panel (32 rows per block)", "k_update": "sweep: trailing update, 8 waves",
     "k_gemm128": "sweep: early-diagonal chain (two 128^3 products)", "k_gate": "sweep: gate hint", "k_copy_panel": "sweep: column panel copy (full sweep, pivoted)",
     "k_copy_panel_sym": "half sweep: column panel from the upper triangle", "k_mirror_upper": "half sweep: mirror", "k_symmetrize": "full sweep / pivoted: average the triangles",
-    "k_add_diag": "corner fix after the shifted sweep", "k_cvec": "c = A^-1[:, :N] Z", "k_matvec": "probe of the inverse", "k_matvec3": "probe of the inverse",
+    "k_add_diag": "corner fix after the shifted sweep", "k_cvec": "mik_factor: c = A^-1[:, :N] z", "k_matvec": "probe of the inverse", "k_matvec3": "probe of the inverse",
     # K2 fallbacks: pivoted path (failed probe / non-SPD / custom variogram), pseudo-inverses (pseudo_inv=True)
     "k_piv_first": "pivoted fallback", "k_piv_step": "pivoted fallback", "k_swap_rows": "pivoted fallback", "k_swap_cols": "pivoted fallback",
     "k_transpose_rows": "pivoted fallback", "k_coo_add": "pseudo_inv: deflated inverse (duplicated stations)", "k_shift_diag": "pseudo_inv: null-space inverse",
@@ -67,12 +67,23 @@ REACHABLE = {
     "k_bj_rotate": "pseudo_inv: block Jacobi",
     # K3
     "k_rhs": "right-hand sides + z (8 variogram ids x NDIM; spherical: candidate tiles, 16- or 8-station flags)", "k_contract": "dense contraction (3 forms, see below)",
-    "k_ss_reduce": "sigma^2 from the row-block partial sums", "k_contract_spg": "range-aware contraction, gathered row groups (default for spherical)",
+    "k_ss_reduce": "dense path: sigma^2 from the row-block partial sums", "k_contract_spg": "range-aware contraction, gathered row groups (default for spherical)",
     "k_contract_sp": "range-aware contraction, aligned blocks (matrix order > 23 168: 32-bit DMA offsets run out)", "k_ss_reduce_sp": "range-aware: sigma^2",
     "k_sp_cand": "range-aware: candidate tiles", "k_sp_lists_g": "range-aware: lists (gathered)", "k_sp_tiles_g": "range-aware: tile records (gathered)",
     "k_sp_lists": "range-aware: lists (aligned fallback)", "k_sp_tiles": "range-aware: tiles (aligned fallback)",
     "k_ps_keys": "points of a launch in Hilbert order", "k_ps_hist": "point sort", "k_ps_scan": "point sort", "k_ps_scatter": "point sort", "k_ps_gather": "point sort",
     "k_ps_bbox": "point sort", "k_ps_unsort": "point sort",
+    # K3: value fields, cross-validation, fields with gaps, error covariance, block kriging -- one family per kernel, named after the call that launches it
+    "k_cvec_fields": "mik_set_fields + mik_predict, mik_cross_validate_folds: C = A^-1[:, :N] V, 8 fields per block",
+    "k_cv_loo": "mik_cross_validate: leave-one-out, k_cvec_fields's sums with the diagonal epilogue",
+    "k_cv_folds": "mik_cross_validate_folds: per fold gather, Cholesky, L^-1, apply (folds <= 96 stations in LDS / larger in scratch)",
+    "k_gap_factor": "mik_set_field_gaps + mik_predict: per-pattern L^-1 of B[S, S] (patterns <= 96 stations in LDS / larger in place)",
+    "k_gap_w": "fields with gaps: W = L^-1 B[S, :]", "k_gap_g": "fields with gaps: g = L^-1 c0_S", "k_gap_coef": "fields with gaps: c~ = c0 - W^T g",
+    "k_gap_contract": "fields with gaps, per launch: Q = W Bt^T on the matrix cores, squared and summed per 16-row group",
+    "k_gap_ss": "fields with gaps, per launch: the patterns' sigma^2 planes",
+    "k_cov_gamma": "mik_predict_cov: -gamma*(d_pq), 6 named models x NDIM 1 / 2 / 3", "k_cov_gemm": "mik_predict_cov: Yt = Bt B^T, then the upper block triangle of C",
+    "k_rhs_block": "mik_predict_block: block-averaged right-hand sides + z, 6 named models x NDIM 2 / 3",
+    "k_block_gamma": "mik_predict_block: gbar of the block's nodes, 6 named models x NDIM 2 / 3", "k_block_ss": "mik_predict_block: sigma^2 - gbar",
     # moving window
     "k_mw_knn": "neighbour search", "k_mw_knn_lane": "neighbour search, windows <= 16", "k_mw_knn_big": "neighbour search, large windows", "k_mw_pairdist": "custom variogram",
     "k_mw_geo_dist": "geographic windows", "k_mw_rhs": "moving-window right-hand sides (pivoting solvers)", "k_mw_rhs_table": "custom variogram",
@@ -94,6 +105,16 @@ PINNED = {  # families the round-5 review found carrying losers: exactly these i
     "k_sp_tiles_g": {"k_sp_tiles_g<true>"},
     "k_gemm128": {"k_gemm128<0>", "k_gemm128<1>"},
     "k_diag_inv_b": {"k_diag_inv_b<0>"},
+    # the families of the fields / cross-validation / gaps / covariance / block kernels: a new form of any of them has to be declared here
+    "k_cvec_fields": {"k_cvec_fields<8>"},
+    "k_cv_loo": {"k_cv_loo<8>"},
+    "k_cv_folds": {"k_cv_folds<8, false>", "k_cv_folds<8, true>"},
+    "k_gap_factor": {"k_gap_factor<false>", "k_gap_factor<true>"},
+    "k_gap_contract": {"k_gap_contract<2>"},
+    "k_cov_gamma": {"k_cov_gamma<%d, %d>" % (m, d) for m in range(6) for d in (1, 2, 3)},
+    "k_cov_gemm": {"k_cov_gemm<2, 1>", "k_cov_gemm<2, 2>"},
+    "k_rhs_block": {"k_rhs_block<%d, %d>" % (m, d) for m in range(6) for d in (2, 3)},
+    "k_block_gamma": {"k_block_gamma<%d, %d>" % (m, d) for m in range(6) for d in (2, 3)},
 }
 
 
@@ -117,6 +138,16 @@ def test_every_kernel_in_the_library_is_reachable_from_a_default_path_or_a_docum
     assert not sorted(set(REACHABLE) - set(fam)), sorted(set(REACHABLE) - set(fam))
     for name, want in PINNED.items():
         assert fam[name] == want, (name, sorted(fam[name] ^ want))
+    # one parameter list per family (the demangled text between the last "(" and ")"): a kernel that does something else gets a name of its
+    # own, not one more overload of an existing name told apart by its argument types
+    params = {}
+    for line in out.splitlines():
+        m = re.search(r"__device_stub__([A-Za-z_0-9]+)", line)
+        if m:
+            params.setdefault(m.group(1), set()).add(line[line.rindex("(") + 1:line.rindex(")")])
+    assert set(params) == set(fam)
+    overloaded = {k: sorted(v) for k, v in params.items() if len(v) != 1}
+    assert not overloaded, "kernel families with more than one parameter list: %s" % overloaded
     # and the device headers of the library stay the size the prune left them (round-5 review: mik_k_inverse.h <= 1200 lines)
     n = len(open(os.path.join(ROOT, "pykrige_amd", "csrc", "mik_k_inverse.h")).read().split("\n"))
     assert n <= 1200, n
