@@ -407,7 +407,8 @@ int  mik_predict_moving_window(mik_handle *h, int n_closest_points);
  *     (a resident one is reused, like mik_predict); runs on the handle's own device (a device group's members take no part).  B_ii is used as
  *     computed: a zero or non-finite B_ii gives IEEE inf / nan in that entry, nothing is raised.  MIK_EINVAL with pseudo_inv: the identity
  *     needs a regular inverse.
- *   n_closest_points != 0 (windowed form: from the k nearest other stations) is not built: MIK_EINVAL, nothing is computed in its place.
+ *   n_closest_points != 0 (windowed form: from the k nearest other stations) is not built into this call: MIK_EINVAL, nothing is computed in
+ *     its place.  The windowed form is mik_cross_validate_window.
  * The resident points and the results of an earlier predict stay as they are (mik_get_results / mik_get_field_results / mik_take_results
  * still return them, also when this call factors). */
 int  mik_cross_validate(mik_handle *h, int n_closest_points /* 0 = global */, double *zhat_out /* nf x n */, double *ss_out /* n */);
@@ -426,6 +427,24 @@ int  mik_cross_validate(mik_handle *h, int n_closest_points /* 0 = global */, do
  * mik_set_fields or else the problem's values, leaves the resident points and the results of an earlier predict as they are.
  * (Added without a new ABI version: no existing signature or field changed.) */
 int  mik_cross_validate_folds(mik_handle *h, const int32_t *fold /* n */, int nfolds, double *zhat_out /* nf x n */, double *ss_out /* n */);
+
+/* Windowed leave-one-out cross-validation (ABI 9, added without a version step: a library without the symbol is stale): entry i is
+ * station i kriged from its n_closest_points nearest OTHER stations -- what mik_predict_moving_window(k) returns at station i's coordinates
+ * for the problem without station i (same variogram, same adjusted coordinates, same exact_values).  The outputs have mik_cross_validate's
+ * shape: zhat_out max(nf, 1) planes of n doubles (plane f = field f of mik_set_fields, else the problem's values), ss_out n doubles, both
+ * in the station order of mik_problem.  Needs mik_set_problem only, and NO factor: none is built, none is invalidated.
+ *   The queries are the stations in the cell-sorted order the neighbour search already holds them in; station i is left out of its own
+ *   window BY INDEX (k_mw_knn<NDIM, true>, k_mw_knn_lane<NDIM, 16, true>), never by distance: a second station at station i's coordinates is
+ *   a neighbour at distance 0 (with exact_values its value is then the answer and sigma^2 is 0).  Ties, solvers, the redo with pivoting and
+ *   "Singular matrix" (MIK_ESINGULAR) are mik_predict_moving_window's, and so is the treatment of fields: up to G - 2 per pass of the LDL^T
+ *   kernel, plane f bit for bit the one-field call.  mik_timing is filled as by mik_predict_moving_window (mw_kernel, rhs_ms, contract_ms,
+ *   predict_ms).
+ *   MIK_EINVAL: drift terms (ordinary kriging only), n_closest_points < 2 or > n - 1 (only n - 1 other stations exist), fields with gaps,
+ *   and a window beyond the neighbour search in LDS (n_closest_points + 256 > "mw_lds_cap", 7936 by default: the global form is the tool).
+ * Runs on the handle's own device (a device group's members take no part).  The resident points, the results of an earlier predict (device
+ * planes and landing zones, also those handed out by mik_take_results) and a resident factor stay as they are; zhat_out / ss_out are
+ * undefined after an error. */
+int  mik_cross_validate_window(mik_handle *h, int n_closest_points, double *zhat_out /* nf x n */, double *ss_out /* n */);
 
 /* The kriging error covariance between the resident points (ABI 9, added without a version step: a library without the symbol is stale).
  * With b(p) the right-hand side of point p exactly as mik_predict forms it (drift rows, the border row and the exact_values zeroing

@@ -105,6 +105,7 @@ SIGNATURES = {
     "mik_predict_moving_window": (C.c_int, [C.c_void_p, C.c_int]),
     "mik_cross_validate": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "mik_cross_validate_folds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, _dp, _dp]),
+    "mik_cross_validate_window": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "mik_statistics": (C.c_int, [C.c_void_p, _dp, _dp]),
     "mik_experimental_variogram": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(C.c_int32)]),
     "mik_krige_execute": (C.c_int, [C.c_int, C.POINTER(MikProblem), C.POINTER(MikPoints), _dp, _dp]),
@@ -410,6 +411,16 @@ class Handle:
         zhat = np.empty((getattr(self, "_fields", None) or 1, n), dtype=np.float64)
         ss = np.empty(n, dtype=np.float64)
         check(self._lib.mik_cross_validate_folds(self._h, fold.ctypes.data_as(C.POINTER(C.c_int32)), int(nfolds), _ptr(zhat), _ptr(ss)))
+        return zhat, ss
+
+    def cross_validate_window(self, n_closest_points):
+        """mik_cross_validate_window: station i kriged from its n_closest_points nearest OTHER stations (left out of its own window by index),
+        the moving window's search and solvers over the stations as points.  No factor is needed or touched.  Returns (zhat, sigma^2) shaped
+        as cross_validate's, in the caller's station order.  The resident points and results stay as they are."""
+        n = self._n
+        zhat = np.empty((getattr(self, "_fields", None) or 1, n), dtype=np.float64)
+        ss = np.empty(n, dtype=np.float64)
+        check(self._lib.mik_cross_validate_window(self._h, int(n_closest_points), _ptr(zhat), _ptr(ss)))
         return zhat, ss
 
     def statistics(self, n):

@@ -377,6 +377,7 @@ struct mik_handle {
   DevBuf grid_axes, grid_idx;  // mik_set_grid: the axes and (masked style) the slab's compacted cell numbers
   // work
   DevBuf mw_idx, mw_dist, stat_S, stat_x, stat_out;
+  DevBuf cvw;  // mik_cross_validate_window: the call's own result planes (the resident z / ss and the landing zones stay as they are)
   int n_cu = 256;
   int t_state = 0;  // what T holds: 0 nothing, 1 the kriging matrix A (shift 0), 2 its inverse
   // options
@@ -513,7 +514,8 @@ int upload_fields(mik_handle* h, int want);                                     
 int one_predict(mik_handle* h);                                                                                  // mik_predict.hip
 int one_predict_cov(mik_handle* h, double* cov_out);                                                             // mik_predict.hip
 int one_predict_block(mik_handle* h, const double* offsets, int nd);                                             // mik_predict.hip
-int one_predict_mw(mik_handle* h, int n_closest);
+int one_predict_mw(mik_handle* h, int n_closest);                                                               // mik_mw.hip
+int one_cross_validate_window(mik_handle* h, int n_closest, double* zhat_out, double* ss_out);                  // mik_mw.hip
 int one_get_field_sigmasq(mik_handle* h, double* out, long ntot);                                                // mik_predict.hip
 int one_cross_validate(mik_handle* h, double* zhat_out, double* ss_out);                                         // mik_predict.hip
 int one_cross_validate_folds(mik_handle* h, const int32_t* fold, int nfolds, double* zhat_out, double* ss_out);  // mik_predict.hip

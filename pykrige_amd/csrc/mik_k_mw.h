@@ -48,6 +48,8 @@ struct KnnArgs {
   // of all points (todo == nullptr: all points)
   int* todo;
   int* todo_count;
+  // windowed cross-validation (SELF instantiations): the queries are stations, self[t] is the station index of query t
+  const int* self;
 };
 
 // Neighbour search for SMALL windows (K <= KMAX <= 32) over points that arrive in spatial order (the rows of a grid): one LANE
@@ -59,7 +61,9 @@ struct KnnArgs {
 // box's nearest open side (no station outside the box can be closer); lanes that are not -- sparse corners, points far outside
 // the stations, waves whose points are scattered (a shuffled point list) -- are appended to `todo` and finished by k_mw_knn.
 // Reference: cKDTree.query(k) of ok.py:957-960 / ok3d.py:904-908.
-template <int NDIM, int KMAX>
+// SELF (windowed leave-one-out cross-validation, mik_cross_validate_window): query t is station a.self[t], and that one station never
+// enters the list -- left out by its INDEX, not by its distance: a second station at the same coordinates is a neighbour at distance 0.
+template <int NDIM, int KMAX, bool SELF>
 __global__ void __launch_bounds__(64) k_mw_knn_lane(KnnArgs a) {
   __shared__ double sx[64], sy[64], sz[64];
   __shared__ int sid[64];
@@ -78,6 +82,8 @@ __global__ void __launch_bounds__(64) k_mw_knn_lane(KnnArgs a) {
     const bool ok = t < a.npt;
     const long ts = ok ? t : base;  // padding lanes shadow the wave's first point (they write nothing)
     const double qx = a.px[ts], qy = a.py[ts], qz = (NDIM == 3) ? a.pz[ts] : 0.0;
+    int me = -1;
+    if (SELF) me = a.self[ts];
     const int cx = min(a.nx - 1, max(0, (int)floor((qx - a.x0) * a.inv_cell)));
     const int cy = min(a.ny - 1, max(0, (int)floor((qy - a.y0) * a.inv_cell)));
     const int cz = (NDIM == 3) ? min(a.nz - 1, max(0, (int)floor((qz - a.z0) * a.inv_cell))) : 0;
@@ -116,7 +122,7 @@ __global__ void __launch_bounds__(64) k_mw_knn_lane(KnnArgs a) {
                 d2 += dz * dz;
               }
               const int st = sid[s];
-              if (d2 < key[KMAX - 1] || (d2 == key[KMAX - 1] && st < id[KMAX - 1])) {
+              if ((!SELF || st != me) && (d2 < key[KMAX - 1] || (d2 == key[KMAX - 1] && st < id[KMAX - 1]))) {
                 bool placed = false;
 #pragma unroll
                 for (int q = KMAX - 1; q > 0; --q) {
@@ -174,7 +180,8 @@ __global__ void __launch_bounds__(64) k_mw_knn_lane(KnnArgs a) {
   }
 }
 
-template <int NDIM>
+// SELF: as in k_mw_knn_lane -- station a.self[t] is no candidate of query t (by index), so it never reaches the buffer and never tightens tau
+template <int NDIM, bool SELF>
 __global__ void __launch_bounds__(64) k_mw_knn(KnnArgs a) {
   extern __shared__ double knn_lds[];
   const int K = a.K, CAP = a.CAP;
@@ -189,6 +196,8 @@ __global__ void __launch_bounds__(64) k_mw_knn(KnnArgs a) {
   for (long w = blockIdx.x; w < nwork; w += gridDim.x) {
     const long t = a.todo ? (long)a.todo[w] : w;
     const double qx = a.px[t], qy = a.py[t], qz = (NDIM == 3) ? a.pz[t] : 0.0;
+    int me = -1;
+    if (SELF) me = a.self[t];
     int cnt = 0;
     double tau = a.tau0 > 0.0 ? a.tau0 : 1e300;
     bool bounded = a.tau0 > 0.0;
@@ -243,7 +252,7 @@ __global__ void __launch_bounds__(64) k_mw_knn(KnnArgs a) {
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          const bool take = (j0 + u * 64 + l < end) && (d2[u] <= tau);
+          const bool take = (j0 + u * 64 + l < end) && (d2[u] <= tau) && (!SELF || id[u] != me);
           const unsigned long long m = __ballot(take);
           if (take) {
             const int pos = cnt + __popcll(m & below);

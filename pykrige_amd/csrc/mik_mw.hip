@@ -137,29 +137,45 @@ static int mw_chol_class(const mik_handle* h, int K) {
   return 100 * 32 + 8;                // K <= 256: 1024 threads per point
 }
 
-int one_predict_mw(mik_handle* h, int n_closest) {
-  if (!h || !h->have_problem) return fail(MIK_ESTATE, "mik_predict_moving_window: set the problem first");
-  if (!h->have_points) return fail(MIK_ESTATE, "mik_predict_moving_window: set points first");
-  if (h->p != 0) return fail(MIK_EINVAL, "moving-window kriging exists for ordinary kriging only (ok.py:929, ok3d.py:901)");
-  if (n_closest < 2) return fail(MIK_EINVAL, "n_closest_points has to be at least two!");
-  if (n_closest > h->N) return fail(MIK_EINVAL, "n_closest_points exceeds the number of stations");
-  HIPC(hipSetDevice(h->device));
-  MIKC(get_events(h, 2));
-  const long npt = h->npt;
-  const int K = n_closest;
+// candidate buffer of the wave-per-point neighbour search: a power of two >= K + 256 (beyond "mw_lds_cap" the lists live in HBM)
+static int mw_knn_cap(int K) {
+  int cap = 512;
+  while (cap < K + 256) cap <<= 1;
+  return cap;
+}
+// value fields per group: the planes (npt doubles per field, twice over where the job runs in an order of its own) are bounded to ~2 GB
+static int mw_field_group(int nf, long npt, bool permuted) {
+  const long per = (long)(2e9 / (8.0 * (double)npt * (permuted ? 2.0 : 1.0)));
+  return (int)std::max(1L, std::min<long>(nf, per));
+}
+
+// One moving-window job: a list of queries, each kriged from its K nearest stations.  mik_predict_moving_window's job is the resident
+// points; mik_cross_validate_window's is the stations themselves in the cell-sorted order of the search grid, each left out of its own
+// window (self).  run_mw_job is the chunk loop both share: search, right-hand sides, solver choice, field groups, the redo with
+// pivoting and the singular-matrix answer.
+struct MwJob {
+  long npt = 0;
+  const double *qx = nullptr, *qy = nullptr, *qz = nullptr;  // search coordinates in job order (geographic: unit vectors)
+  const double *lon = nullptr, *lat = nullptr;               // geographic: the queries in degrees, job order (k_mw_geo_dist)
+  const int* self = nullptr;      // per query the station that is the query itself and stays out of its window; nullptr = none
+  bool lane = false;              // 64 consecutive queries share a few cells of the station grid (k_mw_knn_lane applies for K <= 16)
+  const unsigned* perm = nullptr; // job order -> caller's order (k_ps_unsort); nullptr = the job runs in the caller's order
+  double *zs = nullptr, *sss = nullptr;  // z, sigma^2 as the solvers write them (job order)
+  double *z = nullptr, *ss = nullptr;    // z, sigma^2 in the caller's order (== zs, sss without perm)
+  int fg = 1;                            // fields per group
+  double *fs = nullptr, *fz = nullptr;   // the group's field planes, fg x npt: job order (with perm only) / caller's order
+  bool landing = true;                   // the planes leave for the landing zones (pin_out / pin_fz); false: for hz (nf x npt, caller's memory)
+  double* hz = nullptr;
+};
+
+// (the caller has recorded evpool[0] on the stream and built the station grid if the search runs in LDS)
+static int run_mw_job(mik_handle* h, int K, const MwJob& J) {
+  const long npt = J.npt;
   const int nf = h->nf;  // value fields (mik_set_fields); 0 = the problem's values
   long solve_chunks = 0;
   h->tm.rhs_ms = h->tm.contract_ms = h->tm.predict_ms = 0.0;
   h->tm.contract_launches = 0;
   h->tm.contract_flops_executed = 0.0;
-  h->nf_done = 0;
-  if (npt == 0) {
-    h->have_results = true;
-    h->nf_done = nf;
-    return MIK_OK;
-  }
-  HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));
-  HIPC(hipEventRecord(h->evpool[0], h->stream));
   // The reference cuts each point's system out of a_all = self._get_kriging_matrix(n); here its entries are computed
   // from the selected stations' coordinates, so no N x N matrix exists on this path (and a factor held by the handle
   // stays valid).
@@ -195,60 +211,20 @@ int one_predict_mw(mik_handle* h, int n_closest) {
   MIKC(h->mw_dist.ensure(sizeof(double) * (size_t)chunk * K));
   MIKC(h->flag.ensure(sizeof(int)));
   HIPC(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  DevBuf su, pu, wd, wi, sysbuf, gtab, gvec, todo;
+  DevBuf su, wd, wi, sysbuf, gtab, gvec, todo;
   if (custom) {
     MIKC(gtab.ensure(sizeof(double) * (size_t)chunk * K * K));
     MIKC(gvec.ensure(sizeof(double) * (size_t)chunk * K));
   }
   const double *sx = h->xs.as<double>(), *sy = h->ys.as<double>(), *sz = h->zs.as<double>();
-  const double *qx = h->px.as<double>(), *qy = h->py.as<double>(), *qz = h->pz.as<double>();
-  if (h->geo) {
-    // neighbours by chord length on the unit sphere (same ordering as great-circle), distances recomputed below
-    MIKC(pu.ensure(sizeof(double) * 3 * (size_t)npt));
-    double* p3 = pu.as<double>();
-    hipLaunchKernelGGL(k_geo_unit, dim3((unsigned)((npt + 255) / 256)), dim3(256), 0, h->stream, qx, qy, (int)npt, p3,
-                       p3 + npt, p3 + 2 * (size_t)npt);
-    qx = p3, qy = p3 + npt, qz = p3 + 2 * (size_t)npt;
-  }
+  const double *qx = J.qx, *qy = J.qy, *qz = J.qz;
   const bool three = h->geo || h->ndim == 3;
   int sgrid = 0;
-  int cap = 512;  // candidate buffer of the wave-per-point neighbour search: a power of two >= K + 256
-  while (cap < K + 256) cap <<= 1;
+  const int cap = mw_knn_cap(K);
   const bool wave_knn = cap <= h->opt_mw_lds_cap;  // default 8192 = 96 KB of LDS; beyond that the lists live in HBM
-  // Small windows over a point list in no spatial order (round 4, second session): the lane-per-point search below needs 64
-  // consecutive points to share a few cells of the station grid.  The points are then put in Hilbert-curve order on the device
-  // (k_ps_*: the sorter of the range-aware contraction), searched and solved in that order -- coordinates gathered once, z and
-  // sigma^2 scattered back at the end -- so a shuffled list costs what the rows of a grid cost.
-  bool mw_sorted = false;
-  double *zout = h->z.as<double>(), *ssout = h->ss.as<double>();
-  if (wave_knn) {
-    MIKC(build_mw_grid(h, std::max(8, std::min(K, 256))));
-    const bool cells = (long)h->grid.nx * h->grid.ny * h->grid.nz > 1;
-    const bool coherent = h->pts_step >= 0.0 && 64.0 * h->pts_step <= 10.0 * h->grid.cell;
-    if (h->opt_mw_knn_lane && h->opt_sort_points != 0 && K <= 16 && cells && !h->geo && !custom && !coherent && h->pts_extent > 0.0 &&
-        npt >= 4096) {
-      const double spacing = h->pts_extent / std::pow((double)npt, 1.0 / h->ndim);  // of a sorted list: a wavefront's 64 points are a patch
-      if (12.0 * spacing <= 10.0 * h->grid.cell) {                                   // ~8 spacings across
-        // (segments of 131 072 points like the contraction's launches: the bounding box and the scan of a segment are ONE workgroup
-        // each -- a single 2^20-point segment spent 0.53 + 2 x 0.39 ms in them, eight segments side by side 0.2 ms in all)
-        const long schunk = std::min<long>(((npt + 127) / 128) * 128, 131072L);
-        if (!(h->ps_valid && h->ps_chunk == schunk)) MIKC(sort_points(h, schunk, (npt + schunk - 1) / schunk));
-        const size_t nbp = sizeof(double) * (size_t)npt;
-        MIKC(h->ps_x.ensure(nbp));
-        MIKC(h->ps_y.ensure(nbp));
-        if (h->ndim == 3) MIKC(h->ps_z.ensure(nbp));
-        MIKC(h->ps_zs.ensure(nbp));
-        MIKC(h->ps_sss.ensure(nbp));
-        hipLaunchKernelGGL(k_ps_gather, dim3((unsigned)((npt + 255) / 256)), dim3(256), 0, h->stream, (const unsigned*)h->ps_idx[0].as<unsigned>(),
-                           npt, qx, qy, h->ndim == 3 ? qz : (const double*)nullptr, h->ps_x.as<double>(), h->ps_y.as<double>(),
-                           h->ndim == 3 ? h->ps_z.as<double>() : (double*)nullptr);
-        qx = h->ps_x.as<double>(), qy = h->ps_y.as<double>();
-        if (h->ndim == 3) qz = h->ps_z.as<double>();
-        zout = h->ps_zs.as<double>(), ssout = h->ps_sss.as<double>();
-        mw_sorted = true;
-      }
-    }
-  } else {
+  const bool permuted = J.perm != nullptr;
+  if (!wave_knn) {
+    if (J.self) return fail(MIK_EINVAL, "moving window: the list search in HBM leaves no station out");  // (mik_cross_validate_window refuses such a K)
     MIKC(wd.ensure(sizeof(double) * (size_t)chunk * K));
     MIKC(wi.ensure(sizeof(int) * (size_t)chunk * K));
     if (h->geo) {  // station unit vectors for the plain scan
@@ -284,23 +260,21 @@ int one_predict_mw(mik_handle* h, int n_closest) {
   // Several value fields: a point's local system does not depend on the values, so the neighbour search and the right-hand sides run once
   // per point chunk and the fields enter only the solver -- k_mw_chol eliminates up to G - 2 of them per pass as further right-hand-side
   // rows (the arithmetic of the single value row, hence the same bits), the other solvers take one field per launch.  The planes (npt
-  // doubles per field, twice over for sorted points) are bounded to ~2 GB by groups of fields; a group after the first repeats the
-  // search.  Plane f leaves for the page-locked landing zones (plane 0 in pin_out, the others in pin_fz) as soon as its group is done.
+  // doubles per field, twice over for a job in an order of its own) are bounded to ~2 GB by groups of fields; a group after the first
+  // repeats the search.  Plane f leaves -- for the page-locked landing zones (plane 0 in pin_out, the others in pin_fz) or for the caller's
+  // array -- as soon as its group is done.
   int rows = 1;  // value rows per solver pass
   if (chol) rows = mw_chol_class(h, K) / 100 - 2;
-  int fg = 1;    // fields per group
+  const int fg = J.fg;
   const double* fv = nullptr;
-  DevBuf splanes;
   if (nf > 0) {
     MIKC(upload_fields(h, 0));  // the caller's station order: the neighbour lists hold the caller's station indices
     fv = h->fv.as<double>();
-    const long per = (long)(2e9 / (8.0 * (double)npt * (mw_sorted ? 2.0 : 1.0)));
-    fg = (int)std::max(1L, std::min<long>(nf, per));
-    MIKC(h->zf.ensure(sizeof(double) * (size_t)fg * (size_t)npt));
-    if (mw_sorted) MIKC(splanes.ensure(sizeof(double) * (size_t)fg * (size_t)npt));
-    HIPC(hipEventSynchronize(h->ev_d2h));  // an earlier predict's copies may still write the landing zones
-    MIKC(h->pin_out.ensure(sizeof(double) * 2 * (size_t)npt));
-    if (nf > 1) MIKC(h->pin_fz.ensure(sizeof(double) * (size_t)(nf - 1) * (size_t)npt));
+    if (J.landing) {
+      HIPC(hipEventSynchronize(h->ev_d2h));  // an earlier predict's copies may still write the landing zones
+      MIKC(h->pin_out.ensure(sizeof(double) * 2 * (size_t)npt));
+      if (nf > 1) MIKC(h->pin_fz.ensure(sizeof(double) * (size_t)(nf - 1) * (size_t)npt));
+    }
   }
   auto solve = [&](const MwArgs& a, long pc) -> int {
     if (big) {
@@ -325,8 +299,8 @@ int one_predict_mw(mik_handle* h, int n_closest) {
   MIKC(get_events(h, 2 + 2 * (size_t)ngroups * (size_t)((npt + chunk - 1) / chunk)));
   for (int g0 = 0; g0 < std::max(nf, 1); g0 += fg) {
     const int gn = nf > 0 ? std::min(fg, nf - g0) : 0;  // fields of this group
-    double* zpl = nf > 0 ? (mw_sorted ? splanes.as<double>() : h->zf.as<double>()) : nullptr;
-    if (g0 > 0) HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));  // the previous group's planes have left
+    double* zpl = nf > 0 ? (permuted ? J.fs : J.fz) : nullptr;
+    if (g0 > 0 && J.landing) HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));  // the previous group's planes have left
     for (long p0 = 0; p0 < npt; p0 += chunk) {
       const long pc = (npt - p0 < chunk) ? npt - p0 : chunk;
       const unsigned kgrid = (unsigned)((pc + 255) / 256);
@@ -368,12 +342,14 @@ int one_predict_mw(mik_handle* h, int n_closest) {
         }
         ka.idx_out = idx;
         ka.dist_out = dist;
+        const bool self = J.self != nullptr;
+        if (self) ka.self = J.self + p0;
         // (measured, profiles/r04_mw_knn_ab.txt: rows of a grid, k = 10: search + rhs 2.65 -> 0.62 ms per 1e6 points, bit-identical; a
         // 32-entry list per lane only ties with the wave-per-point search, and a shuffled point list sends every lane to the list --
         // one same-address atomic per wavefront, +0.3 ms -- hence K <= 16 and the coherence test: 64 consecutive points must span
-        // few cells, judged from the median step between consecutive points that mik_set_points / mik_set_grid recorded)
-        if (h->opt_mw_knn_lane && K <= 16 && (long)h->grid.nx * h->grid.ny * h->grid.nz > 1 &&
-            (mw_sorted || (h->pts_step >= 0.0 && 64.0 * h->pts_step * (h->geo ? MIK_PI / 180.0 : 1.0) <= 10.0 * h->grid.cell))) {
+        // few cells, judged by the job's owner -- one_predict_mw from the median step between consecutive points that mik_set_points /
+        // mik_set_grid recorded; the cell-sorted stations of the cross-validation job are coherent by construction)
+        if (h->opt_mw_knn_lane && K <= 16 && (long)h->grid.nx * h->grid.ny * h->grid.nz > 1 && J.lane) {
           // small windows: one lane per point over the box of cells its wavefront's 64 consecutive points share (k_mw_knn_lane); the
           // wave-per-point kernel below then only walks the list of points that pass left unfinished
           MIKC(todo.ensure(sizeof(int) * ((size_t)pc + 1)));
@@ -381,20 +357,27 @@ int one_predict_mw(mik_handle* h, int n_closest) {
           ka.todo = todo.as<int>() + 1;
           HIPC(hipMemsetAsync(ka.todo_count, 0, sizeof(int), h->stream));
           const unsigned lgrid = (unsigned)std::min<long>((pc + 63) / 64, 64L * h->n_cu);
-          if (three) hipLaunchKernelGGL((k_mw_knn_lane<3, 16>), dim3(lgrid), dim3(64), 0, h->stream, ka);
-          else hipLaunchKernelGGL((k_mw_knn_lane<2, 16>), dim3(lgrid), dim3(64), 0, h->stream, ka);
+          if (self) {
+            if (three) hipLaunchKernelGGL((k_mw_knn_lane<3, 16, true>), dim3(lgrid), dim3(64), 0, h->stream, ka);
+            else hipLaunchKernelGGL((k_mw_knn_lane<2, 16, true>), dim3(lgrid), dim3(64), 0, h->stream, ka);
+          } else {
+            if (three) hipLaunchKernelGGL((k_mw_knn_lane<3, 16, false>), dim3(lgrid), dim3(64), 0, h->stream, ka);
+            else hipLaunchKernelGGL((k_mw_knn_lane<2, 16, false>), dim3(lgrid), dim3(64), 0, h->stream, ka);
+          }
         }
+        const void* kfn = three ? (self ? (const void*)k_mw_knn<3, true> : (const void*)k_mw_knn<3, false>)
+                                : (self ? (const void*)k_mw_knn<2, true> : (const void*)k_mw_knn<2, false>);
+        HIPC(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)klds));
         if (three) {
-          HIPC(hipFuncSetAttribute((const void*)k_mw_knn<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)klds));
-          hipLaunchKernelGGL(k_mw_knn<3>, dim3(wgrid), dim3(64), klds, h->stream, ka);
+          if (self) hipLaunchKernelGGL((k_mw_knn<3, true>), dim3(wgrid), dim3(64), klds, h->stream, ka);
+          else hipLaunchKernelGGL((k_mw_knn<3, false>), dim3(wgrid), dim3(64), klds, h->stream, ka);
         } else {
-          HIPC(hipFuncSetAttribute((const void*)k_mw_knn<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)klds));
-          hipLaunchKernelGGL(k_mw_knn<2>, dim3(wgrid), dim3(64), klds, h->stream, ka);
+          if (self) hipLaunchKernelGGL((k_mw_knn<2, true>), dim3(wgrid), dim3(64), klds, h->stream, ka);
+          else hipLaunchKernelGGL((k_mw_knn<2, false>), dim3(wgrid), dim3(64), klds, h->stream, ka);
         }
       }
       if (h->geo)
-        hipLaunchKernelGGL(k_mw_geo_dist, dim3((unsigned)((pc * K + 255) / 256)), dim3(256), 0, h->stream,
-                           (const double*)h->px.as<double>() + p0, (const double*)h->py.as<double>() + p0, pc, K,
+        hipLaunchKernelGGL(k_mw_geo_dist, dim3((unsigned)((pc * K + 255) / 256)), dim3(256), 0, h->stream, J.lon + p0, J.lat + p0, pc, K,
                            (const double*)h->xs.as<double>(), (const double*)h->ys.as<double>(), (const int*)idx, dist);
       MwArgs a{};
       a.sx = h->xs.as<double>();
@@ -409,8 +392,8 @@ int one_predict_mw(mik_handle* h, int n_closest) {
       a.v = h->v;
       a.exact = h->exact;
       a.eps = h->eps;
-      a.z = zout + p0;
-      a.ss = ssout + p0;
+      a.z = J.zs + p0;
+      a.ss = J.sss + p0;
       a.flag = h->flag.as<int>();
       a.nrow = 1;
       a.zstride = h->N;
@@ -453,35 +436,37 @@ int one_predict_mw(mik_handle* h, int n_closest) {
       ++solve_chunks;
       HIPC(hipGetLastError());
     }
-    const unsigned* perm = mw_sorted ? (const unsigned*)h->ps_idx[0].as<unsigned>() : nullptr;
     const unsigned ugrid = (unsigned)((npt + 255) / 256);
     if (nf == 0) {
-      if (mw_sorted)  // back to the caller's order
-        hipLaunchKernelGGL(k_ps_unsort, dim3(ugrid), dim3(256), 0, h->stream, perm, npt, (const double*)zout, (const double*)ssout, h->z.as<double>(),
-                           h->ss.as<double>());
+      if (permuted)  // back to the caller's order
+        hipLaunchKernelGGL(k_ps_unsort, dim3(ugrid), dim3(256), 0, h->stream, J.perm, npt, (const double*)J.zs, (const double*)J.sss, J.z, J.ss);
     } else {
-      if (mw_sorted) {  // sigma^2 and the group's planes back to the caller's order, two per launch (sigma^2 again beside an odd last plane)
+      if (permuted) {  // sigma^2 and the group's planes back to the caller's order, two per launch (sigma^2 again beside an odd last plane)
         for (int q = -1; q < gn; q += 2) {
-          const double* s0 = q < 0 ? ssout : splanes.as<double>() + (size_t)q * npt;
-          double* d0 = q < 0 ? h->ss.as<double>() : h->zf.as<double>() + (size_t)q * npt;
+          const double* s0 = q < 0 ? J.sss : J.fs + (size_t)q * npt;
+          double* d0 = q < 0 ? J.ss : J.fz + (size_t)q * npt;
           const bool pair = q + 1 < gn;
-          const double* s1 = pair ? splanes.as<double>() + (size_t)(q + 1) * npt : ssout;
-          double* d1 = pair ? h->zf.as<double>() + (size_t)(q + 1) * npt : h->ss.as<double>();
-          hipLaunchKernelGGL(k_ps_unsort, dim3(ugrid), dim3(256), 0, h->stream, perm, npt, s0, s1, d0, d1);
+          const double* s1 = pair ? J.fs + (size_t)(q + 1) * npt : J.sss;
+          double* d1 = pair ? J.fz + (size_t)(q + 1) * npt : J.ss;
+          hipLaunchKernelGGL(k_ps_unsort, dim3(ugrid), dim3(256), 0, h->stream, J.perm, npt, s0, s1, d0, d1);
         }
       }
-      // the group's planes leave for the landing zones behind the solves
-      HIPC(hipEventRecord(h->evpool[1], h->stream));
-      HIPC(hipStreamWaitEvent(h->stream_d2h, h->evpool[1], 0));
-      for (int f = 0; f < gn; ++f) {
-        const int fi = g0 + f;
-        double* dst = fi == 0 ? h->pin_out.as<double>() : h->pin_fz.as<double>() + (size_t)(fi - 1) * npt;
-        HIPC(hipMemcpyAsync(dst, h->zf.as<double>() + (size_t)f * npt, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
+      if (J.landing) {
+        // the group's planes leave for the landing zones behind the solves
+        HIPC(hipEventRecord(h->evpool[1], h->stream));
+        HIPC(hipStreamWaitEvent(h->stream_d2h, h->evpool[1], 0));
+        for (int f = 0; f < gn; ++f) {
+          const int fi = g0 + f;
+          double* dst = fi == 0 ? h->pin_out.as<double>() : h->pin_fz.as<double>() + (size_t)(fi - 1) * npt;
+          HIPC(hipMemcpyAsync(dst, J.fz + (size_t)f * npt, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
+        }
+        HIPC(hipEventRecord(h->ev_d2h, h->stream_d2h));
+      } else {
+        // ... or for the caller's planes, in stream order (the next group overwrites the device planes only behind these copies)
+        HIPC(hipMemcpyAsync(J.hz + (size_t)g0 * npt, J.fz, sizeof(double) * (size_t)gn * npt, hipMemcpyDeviceToHost, h->stream));
       }
-      HIPC(hipEventRecord(h->ev_d2h, h->stream_d2h));
     }
   }
-  h->tm.points_sorted = mw_sorted ? 1 : 0;
   int flag = 0;
   HIPC(hipMemcpyAsync(&flag, h->flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPC(hipEventRecord(h->evpool[1], h->stream));
@@ -497,17 +482,157 @@ int one_predict_mw(mik_handle* h, int n_closest) {
   h->tm.mw_kernel = chol ? 1 : cholb ? 4 : (big ? 3 : 2);
   h->tm.rhs_ms = h->tm.predict_ms - h->tm.contract_ms;  // neighbour search + right-hand sides
   if ((flag & 2) && !mw_piv) {  // a local system was not positive definite after the shift: redo with partial pivoting
+    HIPC(hipEventRecord(h->evpool[0], h->stream));
     h->mw_force_piv = true;
-    const int rc = one_predict_mw(h, n_closest);
+    const int rc = run_mw_job(h, K, J);
     h->mw_force_piv = false;
     return rc;
   }
   if (flag) return fail(MIK_ESINGULAR, "Singular matrix");  // cok.pyx:176-177
+  return MIK_OK;
+}
+
+int one_predict_mw(mik_handle* h, int n_closest) {
+  if (!h || !h->have_problem) return fail(MIK_ESTATE, "mik_predict_moving_window: set the problem first");
+  if (!h->have_points) return fail(MIK_ESTATE, "mik_predict_moving_window: set points first");
+  if (h->p != 0) return fail(MIK_EINVAL, "moving-window kriging exists for ordinary kriging only (ok.py:929, ok3d.py:901)");
+  if (n_closest < 2) return fail(MIK_EINVAL, "n_closest_points has to be at least two!");
+  if (n_closest > h->N) return fail(MIK_EINVAL, "n_closest_points exceeds the number of stations");
+  HIPC(hipSetDevice(h->device));
+  MIKC(get_events(h, 2));
+  const long npt = h->npt;
+  const int K = n_closest;
+  const int nf = h->nf;
+  h->tm.rhs_ms = h->tm.contract_ms = h->tm.predict_ms = 0.0;
+  h->tm.contract_launches = 0;
+  h->tm.contract_flops_executed = 0.0;
+  h->nf_done = 0;
+  if (npt == 0) {
+    h->have_results = true;
+    h->nf_done = nf;
+    return MIK_OK;
+  }
+  HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));
+  HIPC(hipEventRecord(h->evpool[0], h->stream));
+  const bool custom = h->model == MIK_MODEL_CUSTOM;
+  MwJob J;
+  J.npt = npt;
+  J.qx = h->px.as<double>(), J.qy = h->py.as<double>(), J.qz = h->pz.as<double>();
+  J.lon = h->px.as<double>(), J.lat = h->py.as<double>();
+  DevBuf pu, splanes;
+  if (h->geo) {
+    // neighbours by chord length on the unit sphere (same ordering as great-circle), distances recomputed below
+    MIKC(pu.ensure(sizeof(double) * 3 * (size_t)npt));
+    double* p3 = pu.as<double>();
+    hipLaunchKernelGGL(k_geo_unit, dim3((unsigned)((npt + 255) / 256)), dim3(256), 0, h->stream, J.qx, J.qy, (int)npt, p3,
+                       p3 + npt, p3 + 2 * (size_t)npt);
+    J.qx = p3, J.qy = p3 + npt, J.qz = p3 + 2 * (size_t)npt;
+  }
+  // Small windows over a point list in no spatial order (round 4, second session): the lane-per-point search needs 64
+  // consecutive points to share a few cells of the station grid.  The points are then put in Hilbert-curve order on the device
+  // (k_ps_*: the sorter of the range-aware contraction), searched and solved in that order -- coordinates gathered once, z and
+  // sigma^2 scattered back at the end -- so a shuffled list costs what the rows of a grid cost.
+  bool mw_sorted = false;
+  J.zs = J.z = h->z.as<double>(), J.sss = J.ss = h->ss.as<double>();
+  if (mw_knn_cap(K) <= h->opt_mw_lds_cap) {
+    MIKC(build_mw_grid(h, std::max(8, std::min(K, 256))));
+    const bool cells = (long)h->grid.nx * h->grid.ny * h->grid.nz > 1;
+    const bool coherent = h->pts_step >= 0.0 && 64.0 * h->pts_step <= 10.0 * h->grid.cell;
+    if (h->opt_mw_knn_lane && h->opt_sort_points != 0 && K <= 16 && cells && !h->geo && !custom && !coherent && h->pts_extent > 0.0 &&
+        npt >= 4096) {
+      const double spacing = h->pts_extent / std::pow((double)npt, 1.0 / h->ndim);  // of a sorted list: a wavefront's 64 points are a patch
+      if (12.0 * spacing <= 10.0 * h->grid.cell) {                                   // ~8 spacings across
+        // (segments of 131 072 points like the contraction's launches: the bounding box and the scan of a segment are ONE workgroup
+        // each -- a single 2^20-point segment spent 0.53 + 2 x 0.39 ms in them, eight segments side by side 0.2 ms in all)
+        const long schunk = std::min<long>(((npt + 127) / 128) * 128, 131072L);
+        if (!(h->ps_valid && h->ps_chunk == schunk)) MIKC(sort_points(h, schunk, (npt + schunk - 1) / schunk));
+        const size_t nbp = sizeof(double) * (size_t)npt;
+        MIKC(h->ps_x.ensure(nbp));
+        MIKC(h->ps_y.ensure(nbp));
+        if (h->ndim == 3) MIKC(h->ps_z.ensure(nbp));
+        MIKC(h->ps_zs.ensure(nbp));
+        MIKC(h->ps_sss.ensure(nbp));
+        hipLaunchKernelGGL(k_ps_gather, dim3((unsigned)((npt + 255) / 256)), dim3(256), 0, h->stream, (const unsigned*)h->ps_idx[0].as<unsigned>(),
+                           npt, J.qx, J.qy, h->ndim == 3 ? J.qz : (const double*)nullptr, h->ps_x.as<double>(), h->ps_y.as<double>(),
+                           h->ndim == 3 ? h->ps_z.as<double>() : (double*)nullptr);
+        J.qx = h->ps_x.as<double>(), J.qy = h->ps_y.as<double>();
+        if (h->ndim == 3) J.qz = h->ps_z.as<double>();
+        J.zs = h->ps_zs.as<double>(), J.sss = h->ps_sss.as<double>();
+        J.perm = (const unsigned*)h->ps_idx[0].as<unsigned>();
+        mw_sorted = true;
+      }
+    }
+    J.lane = mw_sorted || (h->pts_step >= 0.0 && 64.0 * h->pts_step * (h->geo ? MIK_PI / 180.0 : 1.0) <= 10.0 * h->grid.cell);
+  }
+  if (nf > 0) {
+    J.fg = mw_field_group(nf, npt, mw_sorted);
+    MIKC(h->zf.ensure(sizeof(double) * (size_t)J.fg * (size_t)npt));
+    J.fz = h->zf.as<double>();
+    if (mw_sorted) {
+      MIKC(splanes.ensure(sizeof(double) * (size_t)J.fg * (size_t)npt));
+      J.fs = splanes.as<double>();
+    }
+  }
+  h->tm.points_sorted = mw_sorted ? 1 : 0;
+  MIKC(run_mw_job(h, K, J));
   MIKC(h->pin_out.ensure(sizeof(double) * 2 * (size_t)npt));
   if (nf == 0) HIPC(hipMemcpyAsync(h->pin_out.as<double>(), h->z.p, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
   HIPC(hipMemcpyAsync(h->pin_out.as<double>() + npt, h->ss.p, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
   HIPC(hipEventRecord(h->ev_d2h, h->stream_d2h));
   h->have_results = true;
   h->nf_done = nf;
+  return MIK_OK;
+}
+
+// Windowed leave-one-out cross-validation (mik_cross_validate_window): the job is the stations themselves, in the cell-sorted order the
+// search grid already holds them in (G.gx / gy / gz, G.orig) -- 64 consecutive queries share a few cells by construction, so the lane
+// search applies for K <= 16 on any grid of more than one cell, without a point sort.  Query t is station orig[t] and stays out of its own
+// window by index (KnnArgs::self).  Results land in buffers of this call (cvw) and are scattered back through orig (k_ps_unsort); the
+// resident points, h->z / h->ss, the landing zones, have_results and a resident factor are not touched.
+int one_cross_validate_window(mik_handle* h, int n_closest, double* zhat_out, double* ss_out) {
+  if (h->p != 0) return fail(MIK_EINVAL, "moving-window kriging exists for ordinary kriging only (ok.py:929, ok3d.py:901)");
+  if (n_closest < 2) return fail(MIK_EINVAL, "n_closest_points has to be at least two!");
+  const long N = h->N;
+  const int K = n_closest;
+  if (K > N - 1)
+    return fail(MIK_EINVAL, "mik_cross_validate_window: n_closest_points = " + std::to_string(K) + " exceeds the number of OTHER stations (" +
+                                std::to_string(N - 1) + ")");
+  if (mw_knn_cap(K) > h->opt_mw_lds_cap)
+    return fail(MIK_EINVAL, "mik_cross_validate_window: a window of " + std::to_string(K) + " stations is beyond the neighbour search in LDS (\"mw_lds_cap\" " +
+                                std::to_string(h->opt_mw_lds_cap) + " candidates: n_closest_points <= " + std::to_string(h->opt_mw_lds_cap - 256) +
+                                "); at that window size the global form, mik_cross_validate, is the tool");
+  HIPC(hipSetDevice(h->device));
+  MIKC(get_events(h, 2));
+  const int nf = h->nf;
+  HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));
+  HIPC(hipEventRecord(h->evpool[0], h->stream));
+  MIKC(build_mw_grid(h, std::max(8, std::min(K, 256))));
+  const auto& G = h->grid;
+  MwJob J;
+  J.npt = N;
+  J.qx = G.gx.as<double>(), J.qy = G.gy.as<double>(), J.qz = G.gz.as<double>();
+  J.self = G.orig.as<int>();
+  J.perm = (const unsigned*)G.orig.as<unsigned>();  // (station indices: non-negative)
+  J.lane = true;
+  J.landing = false;
+  J.hz = zhat_out;
+  if (nf > 0) J.fg = mw_field_group(nf, N, true);
+  // one buffer of this call: z, sigma^2 in job order and in the caller's order | geographic: lon, lat of the queries | the field planes twice
+  const size_t n = (size_t)N, planes = 4 + (h->geo ? 2 : 0) + (nf > 0 ? 2 * (size_t)J.fg : 0);
+  MIKC(h->cvw.ensure(sizeof(double) * planes * n));
+  double* w = h->cvw.as<double>();
+  J.zs = w, J.sss = w + n, J.z = w + 2 * n, J.ss = w + 3 * n;
+  w += 4 * n;
+  if (h->geo) {  // the queries' lon / lat for the great-circle distances, gathered once
+    hipLaunchKernelGGL(k_ps_gather, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, J.perm, N, (const double*)h->xs.as<double>(),
+                       (const double*)h->ys.as<double>(), (const double*)nullptr, w, w + n, (double*)nullptr);
+    J.lon = w, J.lat = w + n;
+    w += 2 * n;
+  }
+  if (nf > 0) J.fs = w, J.fz = w + (size_t)J.fg * n;
+  MIKC(run_mw_job(h, K, J));
+  if (nf == 0) HIPC(hipMemcpyAsync(zhat_out, J.z, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+  HIPC(hipMemcpyAsync(ss_out, J.ss, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+  HIPC(hipStreamSynchronize(h->stream));
   return MIK_OK;
 }

@@ -1671,6 +1671,15 @@ int mik_cross_validate_folds(mik_handle* h, const int32_t* fold, int nfolds, dou
   return one_cross_validate_folds(h, fold, nfolds, zhat_out, ss_out);
 }
 
+// Windowed leave-one-out: no factor is needed, built or invalidated; the rules are mik_predict_moving_window's (one_cross_validate_window, mik_mw.hip).
+int mik_cross_validate_window(mik_handle* h, int n_closest, double* zhat_out, double* ss_out) {
+  if (!h || !zhat_out || !ss_out) return fail(MIK_EINVAL, "mik_cross_validate_window: NULL argument");
+  if (!h->have_problem) return fail(MIK_ESTATE, "mik_cross_validate_window: set the problem first");
+  if (h->gaps_any) return fail(MIK_EINVAL, "mik_cross_validate_window: fields with gaps (mik_set_field_gaps) are kriged by mik_predict only");
+  MIKC(join_exchange(h));
+  return one_cross_validate_window(h, n_closest, zhat_out, ss_out);
+}
+
 int mik_statistics(mik_handle* h, double* k_out, double* ss_out) {
   if (!h || !k_out || !ss_out) return fail(MIK_EINVAL, "mik_statistics: NULL argument");
   if (!h->have_problem) return fail(MIK_ESTATE, "mik_statistics: set the problem first");

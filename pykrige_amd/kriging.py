@@ -945,7 +945,8 @@ class _KrigingBase:
 
         Windowed form (``n_closest_points=k``: station i kriged from its k nearest other stations): not built.  The argument is
         checked by the backend rules of ``execute()`` (the universal-kriging classes raise as for any moving window) and the call then
-        raises ``NotImplementedError``; nothing else is computed in its place.
+        raises ``NotImplementedError``; nothing else is computed in its place.  The windowed form has a call of its own,
+        ``cross_validate_window(n_closest_points)``.
 
         Groups (``folds``, a keyword after the three above; ``None`` is the leave-one-out form described so far).  ``folds=K``, an
         integer with ``2 <= K <= N``, makes K contiguous folds in the order the stations were given in, the first ``N % K`` of
@@ -1007,6 +1008,67 @@ class _KrigingBase:
         return (zhat if v is not None and np.ndim(values) == 2 else zhat[0]), ss
 
     cross_validate.__doc__ = _CV_DOC
+
+    # ---------------------------------------------------------------- windowed leave-one-out cross-validation (mik_cross_validate_window)
+    def cross_validate_window(self, n_closest_points, values=None, backend="loop"):
+        """Windowed leave-one-out cross-validation on the device: every station kriged from its k nearest OTHER stations.
+
+        ``zhat, sigmasq = obj.cross_validate_window(n_closest_points, values=None, backend="loop")``
+
+        The score of the predictor ``execute(..., n_closest_points=k)``: entry i is what an object built from the other N - 1 stations
+        returns from ``execute('points', x_i, y_i[, z_i], n_closest_points=k)`` -- an object with this object's variogram parameters,
+        centre and adjusted coordinates (the variogram is not fitted again without station i).  The anisotropy, ``exact_values`` and
+        the coordinate type are the object's; ``pseudo_inv`` plays no part, as in ``execute()`` with a window.  No kriging matrix of all
+        stations is formed or inverted, so the call also serves station sets for which the global form ``cross_validate()`` has no
+        N x N inverse; a factor that ``execute()`` left on the device is not used.
+
+        ``values`` and the shapes are ``cross_validate()``'s: ``None`` (the object's own values), ``(N,)`` or ``(N, F)``; ``zhat`` is
+        ``(N,)`` for ``None`` or 1-D values and ``(F, N)`` for 2-D values, ``sigmasq`` is ``(N,)`` and does not depend on the values.
+        Both are plain float64 ndarrays in the order the stations were given in.  Several fields share the neighbour search, the
+        right-hand sides and, for windows up to 256, the factorisation of every local system (as in ``execute_fields``): plane f has
+        the bits of the one-field call.
+
+        Station i is left out of its own window by its index, never by its distance: a station coincident with station i stays in the
+        window, at distance 0.  With ``exact_values=True`` its value is then the answer and ``sigmasq`` is 0.  Ties in distance are
+        broken by station index, as in ``execute()``.
+
+        ``n_closest_points`` and ``backend`` follow the moving window of ``execute()``: ``OrdinaryKriging`` and ``OrdinaryKriging3D``
+        take ``backend='loop'`` or ``'C'`` (both run the same device path); the universal-kriging classes have no moving window and
+        raise ``ValueError``; ``n_closest_points <= 1`` raises ``ValueError``.  ``n_closest_points > N - 1`` raises ``ValueError``
+        (only N - 1 other stations exist), and so does a window beyond the device's neighbour search in on-chip memory (more than
+        7936 stations by default): at that window size the global form is the tool.  A singular local system raises as in
+        ``execute()`` (``ValueError('Singular matrix')`` for backend 'C').  ``variogram_model='custom'`` takes the host round trip of
+        the moving window.  ``last_timing`` is set.  The points and results an earlier ``execute()`` left on the device stay as they
+        are."""
+        self._check_backend(backend, n_closest_points)
+        if n_closest_points is None:
+            raise ValueError("cross_validate_window needs n_closest_points (the global form is cross_validate())")
+        v = None if values is None else self._field_values(values)
+        n = int(np.size(self._values()))
+        k = int(n_closest_points)
+        if k > n - 1:
+            raise ValueError("n_closest_points = %d exceeds the number of other stations (N - 1 = %d)" % (k, n - 1))
+        h = self._get_handle()
+        key = self._problem_key()
+        if key is not None:
+            key = (key, h.option_epoch)
+        if key is None or key != getattr(self, "_factor_key", None):  # (a factored problem on the handle is this object's: it stays, with its factor)
+            self._set_problem(h)
+        if v is not None:
+            self._max_fields = max(self._max_fields, v.shape[1])
+            h.set_fields(v.T)
+        try:
+            try:
+                zhat, ss = h.cross_validate_window(k)
+            except np.linalg.LinAlgError as e:
+                if backend == "C":  # as _solve_moving_window
+                    raise ValueError("Singular matrix") from e
+                raise
+            self.last_timing = h.timing()
+        finally:
+            if v is not None:
+                h.set_fields(None)
+        return (zhat if v is not None and np.ndim(values) == 2 else zhat[0]), ss
 
     def _spec_rows(self, style, shape, npt, specified_drift_arrays):
         """uk.py:1217-1274 / uk3d.py:1030-1095: validate + flatten the per-point specified-drift arrays."""
