@@ -487,6 +487,29 @@ int  mik_predict_cov(mik_handle *h, double *cov_out /* npt x npt, row-major */);
  * pseudo_inv, a handle that spans a device group, value fields or gaps being set. */
 int  mik_predict_block(mik_handle *h, const double *offsets /* nd x ndim, ADJUSTED */, int nd);
 
+/* Block kriging through the moving window (ABI 9, added without a version step: a library without the symbol is stale): the resident points
+ * are block centres as for mik_predict_block, and every block is kriged from the n_closest_points stations nearest to its CENTRE -- ascending
+ * by (squared distance, station index), exactly the set and order mik_predict_moving_window selects at the centre.  With s_j the selected
+ * stations and offsets as in mik_predict_block,
+ *     bbar_j = (sum_u g(|centre + offset_u - s_j|)) / nd,   g(d) = 0 if exact_values and d <= eps, else -gamma(d)    node order, one division,
+ *     bbar_k = 1,
+ * the (k + 1) x (k + 1) local system of mik_predict_moving_window gives lam and mu from bbar, and
+ *     z_V = lam . Z_sel,     sigma^2_V = -lam . bbar - mu - gbar,     gbar exactly mik_predict_block's (one per call):
+ * the estimate and the error variance of the arithmetic mean of Z over the nodes, kriged from the window's stations; a nugget averages down
+ * with nd as in mik_predict_block.  No N x N matrix or inverse exists on this path: needs mik_set_problem + mik_set_points, and NO factor --
+ * none is needed, built or invalidated.
+ *   On the device only the right-hand sides are new: k_mw_rhs<MODEL, 2 | 3> (mik_k_mw.h), one thread per (block, selected station), the
+ *   offsets in LDS, nd variogram values per entry, written over the distances the search left; the search, the four local solvers, the redo
+ *   with pivoting, the Hilbert sort of a shuffled point list and "Singular matrix" (MIK_ESINGULAR) are mik_predict_moving_window's; gbar is
+ *   k_block_gamma's value, subtracted once behind the job by k_block_ss.  For the linear and power models the SPD shift of the LDL^T solvers
+ *   is taken from max(-bbar) instead of max(-b): another positive shift of an algebra that holds for any.
+ *   nd = 1 runs the point kernels and skips gbar: the call is mik_predict_moving_window bit for bit.  mik_timing is filled as by
+ *   mik_predict_moving_window (mw_kernel, points_sorted, rhs_ms, contract_ms, predict_ms; gbar and its subtraction count in rhs_ms).
+ *   Results come back through mik_get_results / mik_take_results.
+ * MIK_EINVAL, before anything is launched: nd < 1, nd > 512, a NULL or non-finite offset, geographic coordinates, a custom variogram, a handle
+ * that spans a device group, value fields or gaps being set, drift terms (ordinary kriging only), n_closest_points < 2 or > n. */
+int  mik_predict_block_window(mik_handle *h, const double *offsets /* nd x ndim, ADJUSTED */, int nd, int n_closest_points);
+
 /* Variogram-fit statistics: replaces core._find_statistics -> core._krige (core.py:759-836, 654-756): for
  * i = 1..n-1 station i is kriged from stations 0..i-1.  k_out / ss_out have n entries (entry 0 unused = 0). */
 int  mik_statistics(mik_handle *h, double *k_out, double *ss_out);

@@ -102,6 +102,7 @@ SIGNATURES = {
     "mik_set_custom_variogram": (C.c_int, [C.c_void_p, VARIOGRAM_FN, C.c_void_p]),
     "mik_predict_cov": (C.c_int, [C.c_void_p, _dp]),
     "mik_predict_block": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "mik_predict_block_window": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int]),
     "mik_predict_moving_window": (C.c_int, [C.c_void_p, C.c_int]),
     "mik_cross_validate": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "mik_cross_validate_folds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, _dp, _dp]),
@@ -385,6 +386,15 @@ class Handle:
         if off.ndim != 2:
             raise ValueError("offsets must have shape (nd, ndim)")
         check(self._lib.mik_predict_block(self._h, _ptr(off), int(off.shape[0])))
+
+    def predict_block_window(self, offsets, n_closest_points):
+        """mik_predict_block_window: the resident points as block centres, every block kriged from the n_closest_points stations nearest to its
+        centre.  offsets as for predict_block; no factor is needed or touched.  z and sigma^2 come back through get_results."""
+        self._taken = None
+        off = np.ascontiguousarray(offsets, dtype=np.float64)
+        if off.ndim != 2:
+            raise ValueError("offsets must have shape (nd, ndim)")
+        check(self._lib.mik_predict_block_window(self._h, _ptr(off), int(off.shape[0]), int(n_closest_points)))
 
     def predict_moving_window(self, n_closest_points):
         self._taken = None

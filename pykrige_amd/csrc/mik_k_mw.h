@@ -10,7 +10,8 @@ namespace mik {
 // Moving-window kriging (n_closest_points; ok.py:929-986, 722-758, cok.pyx:98-193, ok3d.py:697-733).
 //   k_mw_knn   : the k nearest stations of every point, ascending distance (cKDTree.query(k=..., eps=0)),
 //                brute force, one wavefront per point (threshold filter + LDS bitonic cuts, see below).
-//   k_mw_rhs   : right-hand sides -gamma(bd) with the eps rule, in place over the distances.
+//   k_mw_rhs   : right-hand sides -gamma(bd) with the eps rule, in place over the distances (points), or their mean over the nodes of a
+//                block around the point (mik_predict_block_window).
 //   k_mw_solve : per point the (k+1) x (k+1) system (a_all[sel][:, sel] computed from the selected stations'
 //                coordinates, ones border, zero corner -- cok.pyx:138-147), solved by Gauss-Jordan
 //                elimination with partial pivoting (dgesv's pivot choice) in the registers of a G x G thread
@@ -339,16 +340,73 @@ k_mw_rhs_table(double* __restrict__ dist, const double* __restrict__ gam, long n
   dist[e] = (exact && d <= eps) ? 0.0 : -gam[e];
 }
 
-// right-hand sides in place: dist[e] (distance to the e-th selected station) -> b = -gamma(d), 0 on an exact hit
-// (cok.pyx:150-158 with check_b_vect, cok.pyx:196-203)
-template <int MODEL>
-__global__ void __launch_bounds__(256) k_mw_rhs(double* __restrict__ dist, long n, Vario v, int exact, double eps) {
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  const double d = dist[e];
-  double b = -vario<MODEL, false>(v, d, d * d);
-  if (exact && d <= eps) b = 0.0;
-  dist[e] = b;
+// right-hand sides in place over the distances of a chunk: entry e = (point, r) is the point's r-th selected station.  Two forms, one
+// argument block:
+//   k_mw_rhs<MODEL, 0>       points: dist[e] (distance to the station) -> b = -gamma(d), 0 on an exact hit
+//                            (cok.pyx:150-158 with check_b_vect, cok.pyx:196-203)
+//   k_mw_rhs<MODEL, 2 | 3>   blocks (mik_predict_block_window; the number is the dimension): the point is a block centre, its nodes are
+//                            centre + off[u], and dist[e] <- bbar = (sum_u g(|node_u - station|)) / nd with g = -gamma, 0 within eps of
+//                            the station -- summed in node order, one division.  The window was chosen by the centre; the distance the
+//                            search left in dist[e] is not read.
+#define MIK_MW_BLOCK_MAXND 512  // (mik_predict_block's limit: the offsets of a block live in LDS)
+struct MwRhsArgs {
+  double* dist;  // in place
+  long n;        // entries of the chunk: points x K
+  Vario v;
+  int exact;
+  double eps;
+  // the block form only
+  const int* idx;              // the chunk's neighbour lists (station indices)
+  int K;
+  const double *qx, *qy, *qz;  // the chunk's centres in JOB order (the order idx and dist are in)
+  const double *sx, *sy, *sz;  // stations
+  const double* off;           // nd x ndim adjusted node offsets, row-major, node order
+  int nd;
+};
+
+template <int MODEL, int BLOCK>
+__global__ void __launch_bounds__(256) k_mw_rhs(const MwRhsArgs a) {
+  if constexpr (BLOCK == 0) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.n) return;
+    const double d = a.dist[e];
+    double b = -vario<MODEL, false>(a.v, d, d * d);
+    if (a.exact && d <= a.eps) b = 0.0;
+    a.dist[e] = b;
+  } else {
+    // the offsets in LDS: every lane reads node u at the same time, a same-address broadcast (k_rhs_block)
+    __shared__ double so[3][MIK_MW_BLOCK_MAXND];
+    const int nd = a.nd;
+    for (int u = threadIdx.x; u < nd; u += 256) {
+      so[0][u] = a.off[(long)u * BLOCK];
+      so[1][u] = a.off[(long)u * BLOCK + 1];
+      so[2][u] = (BLOCK == 3) ? a.off[(long)u * BLOCK + 2] : 0.0;
+    }
+    __syncthreads();
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.n) return;
+    const long pt = e / a.K;
+    const int st = a.idx[e];
+    const double px = a.qx[pt], py = a.qy[pt], pz = (BLOCK == 3) ? a.qz[pt] : 0.0;
+    const double sx = a.sx[st], sy = a.sy[st], sz = (BLOCK == 3) ? a.sz[st] : 0.0;
+    double acc = 0.0;
+    for (int u = 0; u < nd; ++u) {
+      // distance, variogram value and exact test per node as k_rhs_block spells them
+      const double dx = (px + so[0][u]) - sx, dy = (py + so[1][u]) - sy;
+      double s2;
+      if (BLOCK == 3) {
+        const double dz = (pz + so[2][u]) - sz;
+        s2 = fma(dx, dx, fma(dy, dy, dz * dz));
+      } else {
+        s2 = fma(dx, dx, dy * dy);
+      }
+      const double d = (MODEL == 2) ? 0.0 : sqrt(s2);  // gaussian needs d^2 only
+      double g = -vario<MODEL, true>(a.v, d, s2);
+      if (a.exact && ((MODEL == 2) ? (s2 <= a.eps * a.eps) : (d <= a.eps))) g = 0.0;
+      acc = u ? acc + g : g;
+    }
+    a.dist[e] = acc / (double)nd;
+  }
 }
 
 // (k_mw_solve -- the Gauss-Jordan solver with partial pivoting in registers -- lives in mik_k_mw_solve.h: a translation unit of its own, round 6)

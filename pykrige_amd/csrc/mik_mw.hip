@@ -166,7 +166,20 @@ struct MwJob {
   double *fs = nullptr, *fz = nullptr;   // the group's field planes, fg x npt: job order (with perm only) / caller's order
   bool landing = true;                   // the planes leave for the landing zones (pin_out / pin_fz); false: for hz (nf x npt, caller's memory)
   double* hz = nullptr;
+  const double* off = nullptr;           // block kriging (mik_predict_block_window): the nd x ndim adjusted node offsets on the device; the
+  int nd = 0;                            // queries are block centres and the right-hand sides are averaged over the nodes.  nd = 0: points
 };
+
+// k_mw_rhs<model, BLOCK> over rg workgroups (BLOCK 0: points; 2 / 3: block centres in that many dimensions)
+#define MW_RHS(BLOCK, rg, ra)                                                                                  \
+  switch (h->model) {                                                                                          \
+    case 0: hipLaunchKernelGGL((k_mw_rhs<0, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;            \
+    case 1: hipLaunchKernelGGL((k_mw_rhs<1, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;            \
+    case 2: hipLaunchKernelGGL((k_mw_rhs<2, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;            \
+    case 3: hipLaunchKernelGGL((k_mw_rhs<3, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;            \
+    case 4: hipLaunchKernelGGL((k_mw_rhs<4, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;            \
+    default: hipLaunchKernelGGL((k_mw_rhs<5, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;           \
+  }
 
 // (the caller has recorded evpool[0] on the stream and built the station grid if the search runs in LDS)
 static int run_mw_job(mik_handle* h, int K, const MwJob& J) {
@@ -411,14 +424,18 @@ static int run_mw_job(mik_handle* h, int K, const MwJob& J) {
                              a.sx, a.sy, a.sz, a.mode, gtab.as<double>());
           MIKC(custom_roundtrip(h, gtab.as<double>(), pc * K, K, K));
           a.gtab = gtab.as<double>();
-        } else
-        switch (h->model) {
-          case 0: hipLaunchKernelGGL(k_mw_rhs<0>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
-          case 1: hipLaunchKernelGGL(k_mw_rhs<1>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
-          case 2: hipLaunchKernelGGL(k_mw_rhs<2>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
-          case 3: hipLaunchKernelGGL(k_mw_rhs<3>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
-          case 4: hipLaunchKernelGGL(k_mw_rhs<4>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
-          default: hipLaunchKernelGGL(k_mw_rhs<5>, dim3(rg), dim3(256), 0, h->stream, dist, ne, h->v, h->exact, h->eps); break;
+        } else {
+          MwRhsArgs ra{};
+          ra.dist = dist, ra.n = ne, ra.v = h->v, ra.exact = h->exact, ra.eps = h->eps;
+          if (J.nd > 1) {  // block centres: the mean of the nodes' right-hand sides (the job's owner admits Euclidean named models only)
+            ra.idx = idx, ra.K = K;
+            ra.qx = qx + p0, ra.qy = qy + p0, ra.qz = three ? qz + p0 : nullptr;
+            ra.sx = a.sx, ra.sy = a.sy, ra.sz = a.sz;
+            ra.off = J.off, ra.nd = J.nd;
+            if (h->ndim == 3) { MW_RHS(3, rg, ra) } else { MW_RHS(2, rg, ra) }
+          } else {
+            MW_RHS(0, rg, ra)
+          }
         }
       }
       HIPC(hipEventRecord(h->evpool[2 + 2 * solve_chunks], h->stream));
@@ -492,9 +509,11 @@ static int run_mw_job(mik_handle* h, int K, const MwJob& J) {
   return MIK_OK;
 }
 
-int one_predict_mw(mik_handle* h, int n_closest) {
-  if (!h || !h->have_problem) return fail(MIK_ESTATE, "mik_predict_moving_window: set the problem first");
-  if (!h->have_points) return fail(MIK_ESTATE, "mik_predict_moving_window: set points first");
+// The moving window over the resident points: mik_predict_moving_window (nd = 0) and mik_predict_block_window (the points are block
+// centres, offsets the nd x ndim adjusted node offsets on the host).  nd = 1 is a block of one node at its centre: the point form.
+static int predict_mw_body(mik_handle* h, int n_closest, const double* offsets, int nd, const char* name) {
+  if (!h || !h->have_problem) return fail(MIK_ESTATE, std::string(name) + ": set the problem first");
+  if (!h->have_points) return fail(MIK_ESTATE, std::string(name) + ": set points first");
   if (h->p != 0) return fail(MIK_EINVAL, "moving-window kriging exists for ordinary kriging only (ok.py:929, ok3d.py:901)");
   if (n_closest < 2) return fail(MIK_EINVAL, "n_closest_points has to be at least two!");
   if (n_closest > h->N) return fail(MIK_EINVAL, "n_closest_points exceeds the number of stations");
@@ -574,7 +593,27 @@ int one_predict_mw(mik_handle* h, int n_closest) {
     }
   }
   h->tm.points_sorted = mw_sorted ? 1 : 0;
+  DevBuf blk;  // blocks: the node offsets and, behind them, gbar -- this call's
+  if (nd > 1) {
+    const size_t noff = (size_t)nd * (size_t)h->ndim;
+    MIKC(blk.ensure(sizeof(double) * (noff + 1)));
+    HIPC(hipMemcpy(blk.p, offsets, sizeof(double) * noff, hipMemcpyHostToDevice));
+    J.off = blk.as<double>(), J.nd = nd;
+  }
   MIKC(run_mw_job(h, K, J));
+  if (nd > 1) {
+    // sigma^2_V = (-lam . bbar - mu) - gbar: once, behind the job -- a redo with pivoting re-enters run_mw_job and must not subtract twice
+    double* gbar = blk.as<double>() + (size_t)nd * (size_t)h->ndim;
+    HIPC(hipEventRecord(h->evpool[0], h->stream));
+    MIKC(launch_block_gamma(h, J.off, nd, gbar));
+    MIKC(launch_block_ss(h, J.ss, npt, gbar));
+    HIPC(hipEventRecord(h->evpool[1], h->stream));
+    HIPC(hipStreamSynchronize(h->stream));  // the copies below run on another stream, and blk goes out of scope
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, h->evpool[0], h->evpool[1]));
+    h->tm.predict_ms += ms;
+    h->tm.rhs_ms += ms;  // (everything of the call that is not a solve)
+  }
   MIKC(h->pin_out.ensure(sizeof(double) * 2 * (size_t)npt));
   if (nf == 0) HIPC(hipMemcpyAsync(h->pin_out.as<double>(), h->z.p, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
   HIPC(hipMemcpyAsync(h->pin_out.as<double>() + npt, h->ss.p, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
@@ -582,6 +621,12 @@ int one_predict_mw(mik_handle* h, int n_closest) {
   h->have_results = true;
   h->nf_done = nf;
   return MIK_OK;
+}
+
+int one_predict_mw(mik_handle* h, int n_closest) { return predict_mw_body(h, n_closest, nullptr, 0, "mik_predict_moving_window"); }
+
+int one_predict_block_mw(mik_handle* h, const double* offsets, int nd, int n_closest) {
+  return predict_mw_body(h, n_closest, offsets, nd, "mik_predict_block_window");
 }
 
 // Windowed leave-one-out cross-validation (mik_cross_validate_window): the job is the stations themselves, in the cell-sorted order the

@@ -991,6 +991,26 @@ static int launch_rhs_block(mik_handle* h, const Plan& p, const Launch& l, const
   return MIK_OK;
 }
 
+// gbar does not depend on the block: once per call, one workgroup (also mik_predict_block_window's, mik_mw.hip)
+int launch_block_gamma(mik_handle* h, const double* off, int nd, double* gbar) {
+  BlockGammaArgs g{};
+  g.off = off, g.nd = nd, g.v = h->v, g.eps = h->eps, g.gbar = gbar;
+  DISPATCH_BLOCK(h->model, h->ndim, k_block_gamma, dim3(1), dim3(256), h->stream, g);
+  HIPC(hipGetLastError());
+  return MIK_OK;
+}
+
+// ss[0 .. n) -= gbar; k_block_ss counts in int, so a longer range goes in pieces
+int launch_block_ss(mik_handle* h, double* ss, long n, const double* gbar) {
+  const long piece = 1L << 30;
+  for (long t0 = 0; t0 < n; t0 += piece) {
+    const int m = (int)std::min(piece, n - t0);
+    hipLaunchKernelGGL(k_block_ss, dim3((m + 255) / 256), dim3(256), 0, h->stream, ss + t0, m, gbar);
+  }
+  HIPC(hipGetLastError());
+  return MIK_OK;
+}
+
 int one_predict_block(mik_handle* h, const double* offsets, int nd) {
   bool empty = false;
   MIKC(predict_prologue(h, "mik_predict_block", &empty));
@@ -1010,16 +1030,12 @@ int one_predict_block(mik_handle* h, const double* offsets, int nd) {
   double* gbar = blk.as<double>() + noff;
   HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));  // an earlier predict's result copies still read z / ss
   HIPC(hipEventRecord(h->ev_predict0, h->stream));
-  {  // gbar does not depend on the block: once per call, one workgroup
-    BlockGammaArgs g{};
-    g.off = off, g.nd = nd, g.v = h->v, g.eps = h->eps, g.gbar = gbar;
-    DISPATCH_BLOCK(h->model, h->ndim, k_block_gamma, dim3(1), dim3(256), h->stream, g);
-  }
+  MIKC(launch_block_gamma(h, off, nd, gbar));
   for (long c = 0; c < p.nchunks; ++c) {
     const Launch l(p, c);
     MIKC(launch_rhs_block(h, p, l, off, nd));
     MIKC(contract_dense(h, p, l));
-    hipLaunchKernelGGL(k_block_ss, dim3((l.nvalid + 255) / 256), dim3(256), 0, h->stream, h->ss.as<double>() + l.t0, l.nvalid, (const double*)gbar);
+    MIKC(launch_block_ss(h, h->ss.as<double>() + l.t0, l.nvalid, gbar));
     MIKC(copy_out(h, p, l, h->stream));
   }
   HIPC(hipGetLastError());

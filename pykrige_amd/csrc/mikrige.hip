@@ -1637,6 +1637,27 @@ int mik_predict_moving_window(mik_handle* h, int n_closest) {
   return for_each_device(h, [n_closest](int, mik_handle* d) { return one_predict_mw(d, n_closest); });
 }
 
+// Block kriging through the moving window: mik_predict_block's refusals without pseudo_inv (no inverse on this path) and the moving window's;
+// no factor is needed, built or invalidated (one_predict_block_mw, mik_mw.hip).
+int mik_predict_block_window(mik_handle* h, const double* offsets, int nd, int n_closest) {
+  if (!h) return fail(MIK_ESTATE, "mik_predict_block_window: NULL handle");
+  if (!h->have_problem) return fail(MIK_ESTATE, "mik_predict_block_window: set the problem first");
+  if (!h->have_points) return fail(MIK_ESTATE, "mik_predict_block_window: set points first");
+  if (nd < 1 || nd > 512) return fail(MIK_EINVAL, "mik_predict_block_window: nd = " + std::to_string(nd) + " discretisation nodes; 1 to 512 are built");
+  if (!offsets) return fail(MIK_EINVAL, "mik_predict_block_window: no node offsets");
+  if (h->geo) return fail(MIK_EINVAL, "mik_predict_block_window: geographic coordinates (the blocks of a lon / lat grid are not congruent)");
+  if (h->model == MIK_MODEL_CUSTOM) return fail(MIK_EINVAL, "mik_predict_block_window: a custom variogram is evaluated on the host; block kriging is not built for it");
+  if (h->is_kid || !h->kids.empty()) return fail(MIK_EINVAL, "mik_predict_block_window: blocks are not kriged by a device group");
+  if (h->nf > 0 || h->gaps_any) return fail(MIK_EINVAL, "mik_predict_block_window: value fields (mik_set_fields / mik_set_field_gaps) are set; blocks are kriged from the problem's values");
+  for (long i = 0; i < (long)nd * h->ndim; ++i)
+    if (!std::isfinite(offsets[i])) return fail(MIK_EINVAL, "mik_predict_block_window: a node offset is not finite");
+  if (h->p != 0) return fail(MIK_EINVAL, "moving-window kriging exists for ordinary kriging only (ok.py:929, ok3d.py:901)");
+  if (n_closest < 2) return fail(MIK_EINVAL, "n_closest_points has to be at least two!");
+  if (n_closest > h->N) return fail(MIK_EINVAL, "n_closest_points exceeds the number of stations");
+  MIKC(join_exchange(h));
+  return one_predict_block_mw(h, offsets, nd, n_closest);
+}
+
 // The factor of the cross-validation entry points: a resident one is reused, else mik_factor runs -- and the results of an earlier predict stay.
 static int cv_ensure_factor(mik_handle* h) {
   if (h->have_factor) return MIK_OK;

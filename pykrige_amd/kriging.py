@@ -789,7 +789,7 @@ class _KrigingBase:
     def _refuse_custom_and_pinv(self, name, custom_why, pinv_why):
         if self.variogram_model == "custom":
             raise NotImplementedError("%s: variogram_model='custom' is evaluated on the host; %s" % (name, custom_why))
-        if self.pseudo_inv:
+        if pinv_why is not None and self.pseudo_inv:  # (None: the call uses no inverse)
             raise ValueError("%s needs a regular inverse: %s for pseudo_inv=True" % (name, pinv_why))
 
     @staticmethod
@@ -889,7 +889,8 @@ class _KrigingBase:
         raise ``ValueError``; a non-positive or wrong-length ``block_size`` or ``n_disc`` and ``nd > 512`` raise ``ValueError``;
         ``coordinates_type='geographic'`` raises ``ValueError`` (the blocks of a lon / lat grid are not congruent);
         ``pseudo_inv=True`` raises ``ValueError``; a handle that spans a device group raises ``ValueError``;
-        ``variogram_model='custom'`` raises ``NotImplementedError``.  There is no ``n_closest_points``.  ``execute()``,
+        ``variogram_model='custom'`` raises ``NotImplementedError``.  ``n_closest_points`` is not an argument of this call: blocks
+        kriged through the moving window have a call of their own, ``execute_block_window()``.  ``execute()``,
         ``execute_fields()``, ``execute_cov()`` and ``cross_validate()`` are untouched: a call after ``execute_block`` returns the bits
         it returned before."""
 
@@ -919,6 +920,74 @@ class _KrigingBase:
         h, key = self._resident_problem(P, "execute_block", "blocks are kriged on one device")
         h.predict_block(off)
         self._factor_key = key
+        self.last_timing = h.timing()
+        z, ss = h.get_results()
+        return self._finish(z, ss, style, P.shape, None, backend)
+
+    # ---------------------------------------------------------------- block kriging through the moving window (mik_predict_block_window)
+    _BLOCK_WINDOW_DOC = """Block kriging through the moving window: every block kriged from the k stations nearest to its centre.
+
+        ``zvalues, sigmasq = obj.execute_block_window(style, xpoints, ypoints[, zpoints], block_size, n_closest_points, n_disc=4,
+        backend="loop")``
+
+        ``style``, the points (the block CENTRES), ``block_size``, ``n_disc``, the ``nd = prod(n_disc) <= 512`` cell-centred nodes, their
+        order and their adjusted offsets ``T u`` are ``execute_block()``'s; ``n_closest_points`` and ``backend`` follow the moving window of
+        ``execute()``.  No kriging matrix of all stations is formed or inverted, so the call serves station sets that have no N x N
+        inverse, and ``pseudo_inv`` plays no part.
+
+        The definition.  The window of a block is chosen by the centre: the k stations nearest to the adjusted centre ``p``, ascending by
+        (squared distance, station index) -- exactly the set and order ``execute(..., n_closest_points=k)`` selects at ``p``; the nodes do
+        not take part in the choice.  With ``s_j`` the selected stations,
+        ``bbar_j = (sum_u g(|p + T u - s_j|)) / nd`` (summed in node order, one division) with ``g(d) = 0 if exact_values and d <= eps,
+        else -gamma(d)``, and ``bbar_k = 1``.  The ``(k + 1) x (k + 1)`` local system of the moving window gives the weights ``lam`` and
+        the multiplier ``mu`` from ``bbar``; ``z_V = lam . Z_sel`` and ``sigma^2_V = -lam . bbar - mu - gbar`` with ``gbar`` exactly
+        ``execute_block()``'s.  This is the estimate, and the error variance, of the ARITHMETIC MEAN of ``Z`` over the block's nodes,
+        kriged from the window's stations; a nugget averages down with ``nd`` as in ``execute_block()``.  ``n_disc=1`` is
+        ``execute(style, ..., n_closest_points=k)`` bit for bit.
+
+        ``OrdinaryKriging`` and ``OrdinaryKriging3D`` take ``backend='loop'`` (and ``'C'`` in 2-D; all run the same device path); the
+        universal-kriging classes have no moving window and raise ``ValueError``.  ``style='masked'`` and any unknown style raise
+        ``ValueError``; a non-positive or wrong-length ``block_size`` or ``n_disc`` and ``nd > 512`` raise ``ValueError``;
+        ``n_closest_points <= 1`` and ``n_closest_points > N`` raise ``ValueError``; ``coordinates_type='geographic'`` raises
+        ``ValueError``; a handle that spans a device group raises ``ValueError``; ``variogram_model='custom'`` raises
+        ``NotImplementedError``.  A singular local system raises as in ``execute()`` (``ValueError('Singular matrix')`` for backend
+        'C').  ``last_timing`` is set.  A factor that ``execute()`` left on the device is neither used nor lost, and ``execute()``,
+        ``execute_block()`` and the other calls return after this one the bits they returned before."""
+
+    def _execute_block_window(self, style, axes, block_size, n_closest_points, n_disc, backend):
+        """execute_block_window of the four classes: every argument is checked on the host before the device is touched."""
+        if style == "masked":
+            raise ValueError("execute_block_window: style 'masked' is not built; pass the unmasked block centres as style 'points'")
+        if style != "grid" and style != "points":
+            raise ValueError("style argument must be 'grid' or 'points'")
+        if n_closest_points is None:
+            raise ValueError("execute_block_window needs n_closest_points (the global form is execute_block())")
+        self._check_backend(backend, n_closest_points)
+        off = core.block_node_offsets(self._ndim, block_size, n_disc)
+        if getattr(self, "coordinates_type", "euclidean") == "geographic":
+            raise ValueError("execute_block_window: coordinates_type='geographic' is not built (the blocks of a lon / lat grid are not congruent)")
+        self._refuse_custom_and_pinv("execute_block_window", "block kriging is not built for it", None)
+        self._refuse_group(self._handle, "execute_block_window", "blocks are kriged on one device")
+        k = int(n_closest_points)
+        if k > int(np.size(self._values())):
+            raise ValueError("n_closest_points exceeds the number of stations")  # what mik_predict_moving_window answers execute()
+        off = core.adjust_offsets(off, self._ndim, self._scaling(), self._angle())
+        P = self._prepare(style, axes, None)
+        h = self._get_handle()
+        self._refuse_group(h, "execute_block_window", "blocks are kriged on one device")
+        key = self._problem_key()
+        if key is not None:
+            key = (key, h.option_epoch)
+        if key is None or key != getattr(self, "_factor_key", None):  # (a factored problem on the handle is this object's: it stays, with its factor)
+            self._set_problem(h)
+        self._max_points = max(self._max_points, P.npt)
+        P.load(h, self._ndim, with_extra=False)
+        try:
+            h.predict_block_window(off, k)
+        except np.linalg.LinAlgError as e:
+            if backend == "C":  # as _solve_moving_window
+                raise ValueError("Singular matrix") from e
+            raise
         self.last_timing = h.timing()
         z, ss = h.get_results()
         return self._finish(z, ss, style, P.shape, None, backend)
@@ -1197,6 +1266,11 @@ class OrdinaryKriging(_KrigingBase):
 
     execute_block.__doc__ = _KrigingBase._BLOCK_DOC
 
+    def execute_block_window(self, style, xpoints, ypoints, block_size, n_closest_points, n_disc=4, backend="loop"):
+        return self._execute_block_window(style, (xpoints, ypoints), block_size, n_closest_points, n_disc, backend)
+
+    execute_block_window.__doc__ = _KrigingBase._BLOCK_WINDOW_DOC
+
 
 # =====================================================================================================
 class UniversalKriging(OrdinaryKriging):
@@ -1460,6 +1534,11 @@ class OrdinaryKriging3D(_KrigingBase):
         return self._execute_block(style, (xpoints, ypoints, zpoints), block_size, n_disc, backend)
 
     execute_block.__doc__ = _KrigingBase._BLOCK_DOC
+
+    def execute_block_window(self, style, xpoints, ypoints, zpoints, block_size, n_closest_points, n_disc=4, backend="loop"):
+        return self._execute_block_window(style, (xpoints, ypoints, zpoints), block_size, n_closest_points, n_disc, backend)
+
+    execute_block_window.__doc__ = _KrigingBase._BLOCK_WINDOW_DOC
 
 
 # =====================================================================================================
