@@ -446,6 +446,22 @@ inline int get_events(mik_handle* h, size_t n) {
   return MIK_OK;
 }
 
+// the timing fields every predict of the resident points, and every moving-window job, starts from
+inline void reset_predict_timing(mik_handle* h) {
+  h->tm.rhs_ms = h->tm.contract_ms = h->tm.predict_ms = 0.0;
+  h->tm.contract_launches = 0;
+  h->tm.contract_flops_executed = 0.0;
+}
+
+// what every moving-window entry point refuses; all_stations: the window is bounded by N (a job that leaves the query's own station out
+// has a bound and a message of its own)
+inline int window_refusals(const mik_handle* h, int n_closest, bool all_stations) {
+  if (h->p != 0) return fail(MIK_EINVAL, "moving-window kriging exists for ordinary kriging only (ok.py:929, ok3d.py:901)");
+  if (n_closest < 2) return fail(MIK_EINVAL, "n_closest_points has to be at least two!");
+  if (all_stations && n_closest > h->N) return fail(MIK_EINVAL, "n_closest_points exceeds the number of stations");
+  return MIK_OK;
+}
+
 inline double host_vario(const Vario& v, double d) {
   switch (v.model) {
     case 0: return v.p0 * d + v.p1;

@@ -137,6 +137,13 @@ static int mw_chol_class(const mik_handle* h, int K) {
   return 100 * 32 + 8;                // K <= 256: 1024 threads per point
 }
 
+// byte bounds of a job's work arrays (not options)
+static constexpr double MW_LIST_BYTES = 2e9;   // K > MIK_MW_KMAX: the neighbour lists of a chunk (12 K bytes per point, twice over)
+static constexpr double MW_TABLE_BYTES = 1e9;  // custom variogram: a chunk's K x K pair distances, which visit the host
+static constexpr double MW_CHOLB_BYTES = 6e9;  // blocked Cholesky: the per-block scratch systems in total
+static constexpr double MW_BIG_BYTES = 4e9;    // pivoting LU in HBM: likewise
+static constexpr double MW_PLANE_BYTES = 2e9;  // several value fields: the planes of a field group
+
 // candidate buffer of the wave-per-point neighbour search: a power of two >= K + 256 (beyond "mw_lds_cap" the lists live in HBM)
 static int mw_knn_cap(int K) {
   int cap = 512;
@@ -145,14 +152,14 @@ static int mw_knn_cap(int K) {
 }
 // value fields per group: the planes (npt doubles per field, twice over where the job runs in an order of its own) are bounded to ~2 GB
 static int mw_field_group(int nf, long npt, bool permuted) {
-  const long per = (long)(2e9 / (8.0 * (double)npt * (permuted ? 2.0 : 1.0)));
+  const long per = (long)(MW_PLANE_BYTES / (8.0 * (double)npt * (permuted ? 2.0 : 1.0)));
   return (int)std::max(1L, std::min<long>(nf, per));
 }
 
 // One moving-window job: a list of queries, each kriged from its K nearest stations.  mik_predict_moving_window's job is the resident
 // points; mik_cross_validate_window's is the stations themselves in the cell-sorted order of the search grid, each left out of its own
-// window (self).  run_mw_job is the chunk loop both share: search, right-hand sides, solver choice, field groups, the redo with
-// pivoting and the singular-matrix answer.
+// window (self).  run_mw_job is the loop over field groups and point chunks that both share; what it runs is decided once (plan_mw_job)
+// and issued stage by stage: mw_search, mw_rhs, mw_solve per chunk, mw_deliver per group, mw_read_back at the end.
 struct MwJob {
   long npt = 0;
   const double *qx = nullptr, *qy = nullptr, *qz = nullptr;  // search coordinates in job order (geographic: unit vectors)
@@ -170,105 +177,108 @@ struct MwJob {
   int nd = 0;                            // queries are block centres and the right-hand sides are averaged over the nodes.  nd = 0: points
 };
 
-// k_mw_rhs<model, BLOCK> over rg workgroups (BLOCK 0: points; 2 / 3: block centres in that many dimensions)
-#define MW_RHS(BLOCK, rg, ra)                                                                                  \
-  switch (h->model) {                                                                                          \
-    case 0: hipLaunchKernelGGL((k_mw_rhs<0, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;            \
-    case 1: hipLaunchKernelGGL((k_mw_rhs<1, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;            \
-    case 2: hipLaunchKernelGGL((k_mw_rhs<2, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;            \
-    case 3: hipLaunchKernelGGL((k_mw_rhs<3, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;            \
-    case 4: hipLaunchKernelGGL((k_mw_rhs<4, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;            \
-    default: hipLaunchKernelGGL((k_mw_rhs<5, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;           \
-  }
+// the solver of a job's local systems; the values are timing()'s "mw_kernel"
+//   MW_CHOL   LDL^T of the SPD-shifted system in registers, no pivot search (k_mw_chol's classes; windows up to MIK_MW_CHOL_KMAX)
+//   MW_PIVOT  Gauss-Jordan in registers with implicit partial pivoting (dispatch_mw_solve; windows up to MIK_MW_KMAX)
+//   MW_BIG    LU with partial pivoting in HBM scratch (k_mw_solve_big; any window)
+//   MW_CHOLB  blocked Cholesky of the shifted system, one block per point, panels of 64 in LDS, the matrix in an L2-resident scratch slot
+//             (k_mw_chol_blocked; beyond the register classes, and for smaller windows under "mw_class" 1)
+enum MwSolver { MW_CHOL = 1, MW_PIVOT = 2, MW_BIG = 3, MW_CHOLB = 4 };
 
-// (the caller has recorded evpool[0] on the stream and built the station grid if the search runs in LDS)
-static int run_mw_job(mik_handle* h, int K, const MwJob& J) {
-  const long npt = J.npt;
-  const int nf = h->nf;  // value fields (mik_set_fields); 0 = the problem's values
-  long solve_chunks = 0;
-  h->tm.rhs_ms = h->tm.contract_ms = h->tm.predict_ms = 0.0;
-  h->tm.contract_launches = 0;
-  h->tm.contract_flops_executed = 0.0;
-  // The reference cuts each point's system out of a_all = self._get_kriging_matrix(n); here its entries are computed
-  // from the selected stations' coordinates, so no N x N matrix exists on this path (and a factor held by the handle
-  // stays valid).
-  // K <= MIK_MW_KMAX: candidate lists in registers, systems in LDS, all points in one pass.  Larger K: working sets in
-  // HBM, points in chunks that bound those work arrays to ~2 GB.
-  const int nb = K + 1;
-  const bool custom = h->model == MIK_MODEL_CUSTOM;
-  // small windows are solved without a pivot search on the SPD-shifted local system unless the model cannot promise a
-  // positive definite station block (hole-effect), has no device functor for the shift (custom), or a previous attempt
-  // of this call hit a bad pivot
-  const bool mw_piv = custom || h->model == MIK_MODEL_HOLE_EFFECT || h->mw_force_piv || h->opt_mw_pivot;
-  // three solvers: LDL^T of the shifted system in registers (no pivot search; windows up to 256), Gauss-Jordan in registers
-  // with implicit partial pivoting (when the model cannot promise a positive definite
-  // station block; windows up to 127), LU with partial pivoting in HBM scratch (any window)
-  const bool chol = !mw_piv && K <= MIK_MW_CHOL_KMAX && h->opt_mw_class != 1;
-  // beyond the register classes: blocked Cholesky of the shifted system (one block per point, panels of 64 in LDS, the matrix
-  // in an L2-resident scratch slot); "mw_class" 1 forces it for smaller windows too (A/B runs)
-  const bool cholb = !mw_piv && !chol && K >= 8;
-  const bool big = !chol && !cholb && K > MIK_MW_KMAX;
-  long chunk = npt;
-  if (K > MIK_MW_KMAX) {  // neighbour lists of 12 K bytes per point: bound them to ~2 GB
-    chunk = ((long)(2e9 / (24.0 * K)) / 256) * 256;
-    if (chunk < 256) chunk = 256;
-    if (chunk > npt) chunk = npt;
-  }
-  if (custom) {  // the K x K pair distances of every point visit the host: bound that table to ~1 GB
-    long cc = ((long)(1e9 / (8.0 * K * (K + 1.0))) / 256) * 256;
-    if (cc < 256) cc = 256;
-    if (chunk > cc) chunk = cc;
-    if (chunk > npt) chunk = npt;
-  }
-  MIKC(h->mw_idx.ensure(sizeof(int) * (size_t)chunk * K));
-  MIKC(h->mw_dist.ensure(sizeof(double) * (size_t)chunk * K));
+// what one job runs (plan_mw_job): decided before the first launch, the same for every chunk and group -- and decided anew by the redo
+struct MwPlan {
+  int K, nb, nf;  // window, rows of a local system, value fields (mik_set_fields; 0 = the problem's values)
+  long npt, chunk, nchunks;
+  bool custom, three, permuted;
+  MwSolver solver;
+  bool mw_piv;              // the systems are solved with a pivot search
+  int cap;                  // candidate buffer of the wave-per-point search
+  bool wave_knn, lane;      // the search runs in LDS over the station grid (else: the list scan in HBM); the lane pass runs in front of it
+  int rows, fg, ngroups;    // value rows per solver pass; fields per group, groups
+  int ldc, sgrid;       // MW_CHOLB: leading dimension of a scratch system; MW_CHOLB / MW_BIG: blocks of a solver launch
+  long cslot;           // MW_CHOLB: doubles of a scratch slot
+  size_t sys_bytes, knn_lds, solve_lds;  // all scratch slots; dynamic LDS of k_mw_knn and of k_mw_chol_blocked / k_mw_solve_big
+};
+
+// the work buffers of one call and the station coordinates the list scan reads (geographic: unit vectors in su).  Scoped: released when
+// run_mw_job returns, and it returns only after the stream has drained.
+struct MwWork {
+  DevBuf su, wd, wi, sysbuf, gtab, gvec, todo;
+  const double *sx = nullptr, *sy = nullptr, *sz = nullptr;
+};
+
+// the job's buffers in the sizes of its plan, the cleared singularity flag and, for the list scan, the stations' unit vectors
+static int size_mw_work(mik_handle* h, const MwPlan& p, const MwJob& J, MwWork& w) {
+  const size_t ck = (size_t)p.chunk * (size_t)p.K;
+  MIKC(h->mw_idx.ensure(sizeof(int) * ck));
+  MIKC(h->mw_dist.ensure(sizeof(double) * ck));
   MIKC(h->flag.ensure(sizeof(int)));
   HIPC(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  DevBuf su, wd, wi, sysbuf, gtab, gvec, todo;
-  if (custom) {
-    MIKC(gtab.ensure(sizeof(double) * (size_t)chunk * K * K));
-    MIKC(gvec.ensure(sizeof(double) * (size_t)chunk * K));
+  if (p.custom) {
+    MIKC(w.gtab.ensure(sizeof(double) * ck * (size_t)p.K));
+    MIKC(w.gvec.ensure(sizeof(double) * ck));
   }
-  const double *sx = h->xs.as<double>(), *sy = h->ys.as<double>(), *sz = h->zs.as<double>();
-  const double *qx = J.qx, *qy = J.qy, *qz = J.qz;
-  const bool three = h->geo || h->ndim == 3;
-  int sgrid = 0;
-  const int cap = mw_knn_cap(K);
-  const bool wave_knn = cap <= h->opt_mw_lds_cap;  // default 8192 = 96 KB of LDS; beyond that the lists live in HBM
-  const bool permuted = J.perm != nullptr;
-  if (!wave_knn) {
+  w.sx = h->xs.as<double>(), w.sy = h->ys.as<double>(), w.sz = h->zs.as<double>();
+  if (!p.wave_knn) {
     if (J.self) return fail(MIK_EINVAL, "moving window: the list search in HBM leaves no station out");  // (mik_cross_validate_window refuses such a K)
-    MIKC(wd.ensure(sizeof(double) * (size_t)chunk * K));
-    MIKC(wi.ensure(sizeof(int) * (size_t)chunk * K));
+    MIKC(w.wd.ensure(sizeof(double) * ck));
+    MIKC(w.wi.ensure(sizeof(int) * ck));
     if (h->geo) {  // station unit vectors for the plain scan
-      MIKC(su.ensure(sizeof(double) * 3 * (size_t)h->N));
-      double* s3 = su.as<double>();
-      hipLaunchKernelGGL(k_geo_unit, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, sx, sy, h->N, s3, s3 + h->N,
+      MIKC(w.su.ensure(sizeof(double) * 3 * (size_t)h->N));
+      double* s3 = w.su.as<double>();
+      hipLaunchKernelGGL(k_geo_unit, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, w.sx, w.sy, h->N, s3, s3 + h->N,
                          s3 + 2 * (size_t)h->N);
-      sx = s3, sy = s3 + h->N, sz = s3 + 2 * (size_t)h->N;
+      w.sx = s3, w.sy = s3 + h->N, w.sz = s3 + 2 * (size_t)h->N;
     }
   }
-  int ldc = 0;
-  long cslot = 0;
-  if (cholb) {
-    ldc = ((K + MIK_MWP - 1) / MIK_MWP) * MIK_MWP;
-    cslot = (long)(ldc + MIK_MWP) * ldc + 3L * K;
-    cslot += cslot & 1;
-    long g = (long)(6e9 / (8.0 * (double)cslot));  // per-block scratch systems, <= ~6 GB in total
-    if (g > 2L * h->n_cu) g = 2L * h->n_cu;
-    if (g > chunk) g = chunk;
-    if (g < 1) g = 1;
-    sgrid = (int)g;
-    MIKC(sysbuf.ensure(sizeof(double) * (size_t)cslot * (size_t)sgrid));
-  }
-  if (big) {
-    const double per = 8.0 * nb * (nb + 1.0);
-    long g = (long)(4e9 / per);  // per-block scratch systems, <= ~4 GB in total
-    if (g > 4L * h->n_cu) g = 4L * h->n_cu;
-    if (g > chunk) g = chunk;
-    if (g < 1) g = 1;
-    sgrid = (int)g;
-    MIKC(sysbuf.ensure((size_t)per * (size_t)sgrid));
+  MIKC(w.sysbuf.ensure(p.sys_bytes));
+  if (p.lane) MIKC(w.todo.ensure(sizeof(int) * ((size_t)p.chunk + 1)));
+  return MIK_OK;
+}
+
+// solver, chunk, search and field groups of a job of J.npt queries with windows of K; the work buffers in those sizes
+static int plan_mw_job(mik_handle* h, int K, const MwJob& J, MwPlan& p, MwWork& w) {
+  const long npt = J.npt;
+  p = MwPlan{};
+  p.K = K, p.nb = K + 1, p.nf = h->nf, p.npt = npt;
+  p.custom = h->model == MIK_MODEL_CUSTOM, p.three = h->geo || h->ndim == 3, p.permuted = J.perm != nullptr;
+  // The reference cuts each point's system out of a_all = self._get_kriging_matrix(n); here its entries are computed from the selected
+  // stations' coordinates, so no N x N matrix exists on this path (and a factor held by the handle stays valid).
+  // Small windows are solved without a pivot search on the SPD-shifted local system unless the model cannot promise a positive definite
+  // station block (hole-effect), has no device functor for the shift (custom), or a previous attempt of this call hit a bad pivot.
+  p.mw_piv = p.custom || h->model == MIK_MODEL_HOLE_EFFECT || h->mw_force_piv || h->opt_mw_pivot;
+  const bool chol = !p.mw_piv && K <= MIK_MW_CHOL_KMAX && h->opt_mw_class != 1;
+  const bool cholb = !p.mw_piv && !chol && K >= 8;
+  p.solver = chol ? MW_CHOL : cholb ? MW_CHOLB : K > MIK_MW_KMAX ? MW_BIG : MW_PIVOT;
+  // K <= MIK_MW_KMAX: candidate lists in registers, systems in LDS, all points in one pass.  Larger K: working sets in HBM, points in
+  // chunks that bound the neighbour lists (12 K bytes per point, twice over); custom: the table of pair distances as well
+  long chunk = npt;  // (whole multiples of 256 points, at least 256, at most all)
+  if (K > MIK_MW_KMAX) chunk = std::min(chunk, std::max(256L, ((long)(MW_LIST_BYTES / (24.0 * K)) / 256) * 256));
+  if (p.custom) chunk = std::min(chunk, std::max(256L, ((long)(MW_TABLE_BYTES / (8.0 * K * (K + 1.0))) / 256) * 256));
+  p.chunk = chunk, p.nchunks = (npt + chunk - 1) / chunk;
+  p.cap = mw_knn_cap(K);
+  p.wave_knn = p.cap <= h->opt_mw_lds_cap;  // default 8192 = 96 KB of LDS; beyond that the lists live in HBM
+  p.knn_lds = (size_t)p.cap * (sizeof(double) + sizeof(int));
+  // (measured, profiles/r04_mw_knn_ab.txt: rows of a grid, k = 10: search + rhs 2.65 -> 0.62 ms per 1e6 points, bit-identical; a
+  // 32-entry list per lane only ties with the wave-per-point search, and a shuffled point list sends every lane to the list --
+  // one same-address atomic per wavefront, +0.3 ms -- hence K <= 16 and the coherence test: 64 consecutive points must span
+  // few cells, judged by the job's owner -- one_predict_mw from the median step between consecutive points that mik_set_points /
+  // mik_set_grid recorded; the cell-sorted stations of the cross-validation job are coherent by construction)
+  p.lane = p.wave_knn && h->opt_mw_knn_lane && K <= 16 && (long)h->grid.nx * h->grid.ny * h->grid.nz > 1 && J.lane;
+  if (p.solver == MW_CHOLB) {
+    p.ldc = ((K + MIK_MWP - 1) / MIK_MWP) * MIK_MWP;
+    p.cslot = (long)(p.ldc + MIK_MWP) * p.ldc + 3L * K;
+    p.cslot += p.cslot & 1;
+    const long g = std::min<long>((long)(MW_CHOLB_BYTES / (8.0 * (double)p.cslot)), 2L * h->n_cu);
+    p.sgrid = (int)std::max(1L, std::min(g, chunk));
+    p.sys_bytes = sizeof(double) * (size_t)p.cslot * (size_t)p.sgrid;
+    p.solve_lds = sizeof(double) * 2 * MIK_MWP * MIK_MWP_LD;
+  } else if (p.solver == MW_BIG) {
+    const double per = 8.0 * p.nb * (p.nb + 1.0);
+    const long g = std::min<long>((long)(MW_BIG_BYTES / per), 4L * h->n_cu);
+    p.sgrid = (int)std::max(1L, std::min(g, chunk));
+    p.sys_bytes = (size_t)per * (size_t)p.sgrid;
+    p.solve_lds = sizeof(double) * 2 * (size_t)p.nb + sizeof(int) * (size_t)p.nb;
   }
   // Several value fields: a point's local system does not depend on the values, so the neighbour search and the right-hand sides run once
   // per point chunk and the fields enter only the solver -- k_mw_chol eliminates up to G - 2 of them per pass as further right-hand-side
@@ -276,229 +286,249 @@ static int run_mw_job(mik_handle* h, int K, const MwJob& J) {
   // doubles per field, twice over for a job in an order of its own) are bounded to ~2 GB by groups of fields; a group after the first
   // repeats the search.  Plane f leaves -- for the page-locked landing zones (plane 0 in pin_out, the others in pin_fz) or for the caller's
   // array -- as soon as its group is done.
-  int rows = 1;  // value rows per solver pass
-  if (chol) rows = mw_chol_class(h, K) / 100 - 2;
-  const int fg = J.fg;
-  const double* fv = nullptr;
-  if (nf > 0) {
-    MIKC(upload_fields(h, 0));  // the caller's station order: the neighbour lists hold the caller's station indices
-    fv = h->fv.as<double>();
-    if (J.landing) {
-      HIPC(hipEventSynchronize(h->ev_d2h));  // an earlier predict's copies may still write the landing zones
-      MIKC(h->pin_out.ensure(sizeof(double) * 2 * (size_t)npt));
-      if (nf > 1) MIKC(h->pin_fz.ensure(sizeof(double) * (size_t)(nf - 1) * (size_t)npt));
-    }
+  p.rows = chol ? mw_chol_class(h, K) / 100 - 2 : 1;
+  p.fg = J.fg;
+  p.ngroups = p.nf > 0 ? (p.nf + p.fg - 1) / p.fg : 1;
+  return size_mw_work(h, p, J, w);
+}
+
+// the value fields on the device and, for a job that delivers to them, the landing zones in the size of this job
+static int mw_stage_fields(mik_handle* h, const MwJob& J) {
+  MIKC(upload_fields(h, 0));  // the caller's station order: the neighbour lists hold the caller's station indices
+  if (J.landing) {
+    HIPC(hipEventSynchronize(h->ev_d2h));  // an earlier predict's copies may still write the landing zones
+    MIKC(h->pin_out.ensure(sizeof(double) * 2 * (size_t)J.npt));
+    if (h->nf > 1) MIKC(h->pin_fz.ensure(sizeof(double) * (size_t)(h->nf - 1) * (size_t)J.npt));
   }
-  auto solve = [&](const MwArgs& a, long pc) -> int {
-    if (big) {
-      const size_t lds = sizeof(double) * 2 * (size_t)nb + sizeof(int) * (size_t)nb;
-      if (lds > 150 * 1024) return fail(MIK_EINVAL, "n_closest_points too large for the device path (> ~7600)");
-      const int grid = (int)(pc < sgrid ? pc : sgrid);
-      HIPC(hipFuncSetAttribute((const void*)k_mw_solve_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k_mw_solve_big, dim3(grid), dim3(256), lds, h->stream, a, sysbuf.as<double>());
-    } else if (cholb) {
-      const size_t lds = sizeof(double) * 2 * MIK_MWP * MIK_MWP_LD;
-      const int grid = (int)std::min<long>(sgrid, pc);
-      HIPC(hipFuncSetAttribute((const void*)k_mw_chol_blocked, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k_mw_chol_blocked, dim3(grid), dim3(256), lds, h->stream, a, sysbuf.as<double>(), cslot, ldc);
-    } else if (chol) {
-      MIKC(launch_mw_chol_class(h, a, pc, mw_chol_class(h, K)));
-    } else {
-      MIKC(dispatch_mw_solve(h, a, pc));  // (always the pivoting form: valid for every window, the only one built)
-    }
+  return MIK_OK;
+}
+
+// what the solvers of chunk [p0, p0 + pc) are told: the problem, the chunk's lists and its place in z and sigma^2.  One value row, the
+// problem's; the field loop sets Z, z and nrow per pass, mw_rhs the table of a custom variogram
+static MwArgs mw_args(mik_handle* h, const MwPlan& p, const MwJob& J, long p0, long pc) {
+  MwArgs a{};
+  a.sx = h->xs.as<double>(), a.sy = h->ys.as<double>(), a.sz = h->zs.as<double>();
+  a.mode = h->geo ? 1 : h->ndim, a.K = p.K, a.npt = (int)pc;
+  a.idx = h->mw_idx.as<int>(), a.dist = h->mw_dist.as<double>();
+  a.Z = h->vals.as<double>(), a.v = h->v, a.exact = h->exact, a.eps = h->eps;
+  a.z = J.zs + p0, a.ss = J.sss + p0, a.flag = h->flag.as<int>();
+  a.nrow = 1, a.zstride = h->N, a.pstride = p.npt;
+  return a;
+}
+
+// what the searches over the station grid are told about the grid and the chunk's queries (todo: the lane pass sets it)
+static KnnArgs knn_args(mik_handle* h, const MwPlan& p, const MwJob& J, long p0, long pc) {
+  const auto& G = h->grid;
+  KnnArgs ka{};
+  ka.px = J.qx + p0, ka.py = J.qy + p0, ka.pz = p.three ? J.qz + p0 : nullptr, ka.npt = (int)pc;
+  ka.gx = G.gx.as<double>(), ka.gy = G.gy.as<double>(), ka.gz = G.gz.as<double>();
+  ka.orig = G.orig.as<int>(), ka.cstart = G.cstart.as<int>();
+  ka.N = h->N, ka.K = p.K, ka.CAP = p.cap;
+  ka.nx = G.nx, ka.ny = G.ny, ka.nz = G.nz;
+  ka.x0 = G.x0, ka.y0 = G.y0, ka.z0 = G.z0;
+  ka.inv_cell = 1.0 / G.cell, ka.cell2 = G.cell * G.cell, ka.tau0 = 0.0;
+  if (h->opt_mw_knn_bound && !h->geo && G.live >= 2 && (long)G.nx * G.ny * G.nz > 1) {
+    // radius of the disc / ball expected to hold K + 4 sqrt(K) + 2 of the ~per_cell stations a cell holds; it must stay
+    // inside the 3 x 3 (x 3) cells around the point's cell
+    const double m = p.K + 4.0 * std::sqrt((double)p.K) + 2.0, T = std::max(1.0, G.per_cell);
+    const double r2 = G.live == 3 ? std::pow(m / (4.18879020478639 * T), 2.0 / 3.0) : m / (3.14159265358979 * T);
+    if (r2 <= 1.0) ka.tau0 = r2 * ka.cell2;
+  }
+  ka.idx_out = h->mw_idx.as<int>(), ka.dist_out = h->mw_dist.as<double>();
+  if (J.self) ka.self = J.self + p0;
+  return ka;
+}
+
+// the search over the station grid in NDIM dimensions, SELF: with the query's own station left out.  Small windows: one lane per point
+// over the box of cells its wavefront's 64 consecutive points share (k_mw_knn_lane); the wave-per-point kernel then only walks the list
+// of points that pass left unfinished
+template <int NDIM, bool SELF>
+static int mw_search_grid(mik_handle* h, const MwPlan& p, MwWork& w, KnnArgs ka, long pc) {
+  if (p.lane) {
+    ka.todo_count = w.todo.as<int>();
+    ka.todo = w.todo.as<int>() + 1;
+    HIPC(hipMemsetAsync(ka.todo_count, 0, sizeof(int), h->stream));
+    const unsigned lgrid = (unsigned)std::min<long>((pc + 63) / 64, 64L * h->n_cu);
+    hipLaunchKernelGGL((k_mw_knn_lane<NDIM, 16, SELF>), dim3(lgrid), dim3(64), 0, h->stream, ka);
+  }
+  const unsigned wgrid = (unsigned)std::min<long>(pc, 32L * h->n_cu);
+  HIPC(hipFuncSetAttribute((const void*)k_mw_knn<NDIM, SELF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.knn_lds));
+  hipLaunchKernelGGL((k_mw_knn<NDIM, SELF>), dim3(wgrid), dim3(64), p.knn_lds, h->stream, ka);
+  return MIK_OK;
+}
+
+// the K nearest stations of queries [p0, p0 + pc) into mw_idx / mw_dist: the list scan in HBM, or the searches over the station grid;
+// geographic: the chord lengths the search ordered by become great-circle distances
+static int mw_search(mik_handle* h, const MwPlan& p, MwWork& w, const MwJob& J, long p0, long pc) {
+  int* idx = h->mw_idx.as<int>();
+  double* dist = h->mw_dist.as<double>();
+  if (!p.wave_knn) {
+    hipLaunchKernelGGL(p.three ? k_mw_knn_big<3> : k_mw_knn_big<2>, dim3((unsigned)((pc + 255) / 256)), dim3(256), 0, h->stream, J.qx + p0,
+                       J.qy + p0, p.three ? J.qz + p0 : (const double*)nullptr, (int)pc, w.sx, w.sy, p.three ? w.sz : (const double*)nullptr,
+                       h->N, p.K, w.wd.as<double>(), w.wi.as<int>(), idx, dist);
+  } else {
+    const KnnArgs ka = knn_args(h, p, J, p0, pc);
+    if (p.three) MIKC((J.self ? mw_search_grid<3, true>(h, p, w, ka, pc) : mw_search_grid<3, false>(h, p, w, ka, pc)));
+    else MIKC((J.self ? mw_search_grid<2, true>(h, p, w, ka, pc) : mw_search_grid<2, false>(h, p, w, ka, pc)));
+  }
+  if (h->geo)
+    hipLaunchKernelGGL(k_mw_geo_dist, dim3((unsigned)((pc * p.K + 255) / 256)), dim3(256), 0, h->stream, J.lon + p0, J.lat + p0, pc, p.K,
+                       (const double*)h->xs.as<double>(), (const double*)h->ys.as<double>(), (const int*)idx, dist);
+  return MIK_OK;
+}
+
+// k_mw_rhs<model, BLOCK> over rg workgroups (BLOCK 0: points; 2 / 3: block centres in that many dimensions)
+template <int BLOCK>
+static void launch_mw_rhs(mik_handle* h, unsigned rg, const MwRhsArgs& ra) {
+  switch (h->model) {
+    case 0: hipLaunchKernelGGL((k_mw_rhs<0, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;
+    case 1: hipLaunchKernelGGL((k_mw_rhs<1, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;
+    case 2: hipLaunchKernelGGL((k_mw_rhs<2, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;
+    case 3: hipLaunchKernelGGL((k_mw_rhs<3, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;
+    case 4: hipLaunchKernelGGL((k_mw_rhs<4, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;
+    default: hipLaunchKernelGGL((k_mw_rhs<5, BLOCK>), dim3(rg), dim3(256), 0, h->stream, ra); break;
+  }
+}
+
+// the right-hand sides of the chunk in place over its distances; a custom variogram also leaves the table of its pair semivariances in a
+static int mw_rhs(mik_handle* h, const MwPlan& p, MwWork& w, const MwJob& J, MwArgs& a, long p0, long pc) {
+  const long ne = pc * p.K;
+  const unsigned rg = (unsigned)((ne + 255) / 256);
+  double* dist = h->mw_dist.as<double>();
+  if (p.custom) {
+    // d -> gamma(d) on the host for the point-station distances and for the K x K station pairs of every point
+    HIPC(hipMemcpyAsync(w.gvec.p, dist, sizeof(double) * ne, hipMemcpyDeviceToDevice, h->stream));
+    MIKC(custom_roundtrip(h, w.gvec.as<double>(), pc, p.K, p.K));
+    hipLaunchKernelGGL(k_mw_rhs_table, dim3(rg), dim3(256), 0, h->stream, dist, (const double*)w.gvec.as<double>(), ne, h->exact, h->eps);
+    hipLaunchKernelGGL(k_mw_pairdist, dim3((unsigned)((ne * p.K + 255) / 256)), dim3(256), 0, h->stream, (const int*)a.idx, pc, p.K, a.sx,
+                       a.sy, a.sz, a.mode, w.gtab.as<double>());
+    MIKC(custom_roundtrip(h, w.gtab.as<double>(), pc * p.K, p.K, p.K));
+    a.gtab = w.gtab.as<double>();
     return MIK_OK;
-  };
-  const int ngroups = nf > 0 ? (nf + fg - 1) / fg : 1;
-  MIKC(get_events(h, 2 + 2 * (size_t)ngroups * (size_t)((npt + chunk - 1) / chunk)));
-  for (int g0 = 0; g0 < std::max(nf, 1); g0 += fg) {
-    const int gn = nf > 0 ? std::min(fg, nf - g0) : 0;  // fields of this group
-    double* zpl = nf > 0 ? (permuted ? J.fs : J.fz) : nullptr;
-    if (g0 > 0 && J.landing) HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));  // the previous group's planes have left
-    for (long p0 = 0; p0 < npt; p0 += chunk) {
-      const long pc = (npt - p0 < chunk) ? npt - p0 : chunk;
-      const unsigned kgrid = (unsigned)((pc + 255) / 256);
-      int* idx = h->mw_idx.as<int>();
-      double* dist = h->mw_dist.as<double>();
-      if (!wave_knn) {
-        if (three)
-          hipLaunchKernelGGL(k_mw_knn_big<3>, dim3(kgrid), dim3(256), 0, h->stream, qx + p0, qy + p0, qz + p0, (int)pc, sx, sy, sz,
-                             h->N, K, wd.as<double>(), wi.as<int>(), idx, dist);
-        else
-          hipLaunchKernelGGL(k_mw_knn_big<2>, dim3(kgrid), dim3(256), 0, h->stream, qx + p0, qy + p0, (const double*)nullptr,
-                             (int)pc, sx, sy, (const double*)nullptr, h->N, K, wd.as<double>(), wi.as<int>(), idx, dist);
-      } else {
-        const long wg = 32L * h->n_cu;
-        const unsigned wgrid = (unsigned)(pc < wg ? pc : wg);
-        const size_t klds = (size_t)cap * (sizeof(double) + sizeof(int));
-        KnnArgs ka{};
-        ka.px = qx + p0;
-        ka.py = qy + p0;
-        ka.pz = three ? qz + p0 : nullptr;
-        ka.npt = (int)pc;
-        ka.gx = h->grid.gx.as<double>();
-        ka.gy = h->grid.gy.as<double>();
-        ka.gz = h->grid.gz.as<double>();
-        ka.orig = h->grid.orig.as<int>();
-        ka.cstart = h->grid.cstart.as<int>();
-        ka.N = h->N, ka.K = K, ka.CAP = cap;
-        ka.nx = h->grid.nx, ka.ny = h->grid.ny, ka.nz = h->grid.nz;
-        ka.x0 = h->grid.x0, ka.y0 = h->grid.y0, ka.z0 = h->grid.z0;
-        ka.inv_cell = 1.0 / h->grid.cell;
-        ka.cell2 = h->grid.cell * h->grid.cell;
-        ka.tau0 = 0.0;
-        if (h->opt_mw_knn_bound && !h->geo && h->grid.live >= 2 && (long)h->grid.nx * h->grid.ny * h->grid.nz > 1) {
-          // radius of the disc / ball expected to hold K + 4 sqrt(K) + 2 of the ~per_cell stations a cell holds; it must stay
-          // inside the 3 x 3 (x 3) cells around the point's cell
-          const double m = K + 4.0 * std::sqrt((double)K) + 2.0, T = std::max(1.0, h->grid.per_cell);
-          const double r2 = h->grid.live == 3 ? std::pow(m / (4.18879020478639 * T), 2.0 / 3.0) : m / (3.14159265358979 * T);
-          if (r2 <= 1.0) ka.tau0 = r2 * ka.cell2;
-        }
-        ka.idx_out = idx;
-        ka.dist_out = dist;
-        const bool self = J.self != nullptr;
-        if (self) ka.self = J.self + p0;
-        // (measured, profiles/r04_mw_knn_ab.txt: rows of a grid, k = 10: search + rhs 2.65 -> 0.62 ms per 1e6 points, bit-identical; a
-        // 32-entry list per lane only ties with the wave-per-point search, and a shuffled point list sends every lane to the list --
-        // one same-address atomic per wavefront, +0.3 ms -- hence K <= 16 and the coherence test: 64 consecutive points must span
-        // few cells, judged by the job's owner -- one_predict_mw from the median step between consecutive points that mik_set_points /
-        // mik_set_grid recorded; the cell-sorted stations of the cross-validation job are coherent by construction)
-        if (h->opt_mw_knn_lane && K <= 16 && (long)h->grid.nx * h->grid.ny * h->grid.nz > 1 && J.lane) {
-          // small windows: one lane per point over the box of cells its wavefront's 64 consecutive points share (k_mw_knn_lane); the
-          // wave-per-point kernel below then only walks the list of points that pass left unfinished
-          MIKC(todo.ensure(sizeof(int) * ((size_t)pc + 1)));
-          ka.todo_count = todo.as<int>();
-          ka.todo = todo.as<int>() + 1;
-          HIPC(hipMemsetAsync(ka.todo_count, 0, sizeof(int), h->stream));
-          const unsigned lgrid = (unsigned)std::min<long>((pc + 63) / 64, 64L * h->n_cu);
-          if (self) {
-            if (three) hipLaunchKernelGGL((k_mw_knn_lane<3, 16, true>), dim3(lgrid), dim3(64), 0, h->stream, ka);
-            else hipLaunchKernelGGL((k_mw_knn_lane<2, 16, true>), dim3(lgrid), dim3(64), 0, h->stream, ka);
-          } else {
-            if (three) hipLaunchKernelGGL((k_mw_knn_lane<3, 16, false>), dim3(lgrid), dim3(64), 0, h->stream, ka);
-            else hipLaunchKernelGGL((k_mw_knn_lane<2, 16, false>), dim3(lgrid), dim3(64), 0, h->stream, ka);
-          }
-        }
-        const void* kfn = three ? (self ? (const void*)k_mw_knn<3, true> : (const void*)k_mw_knn<3, false>)
-                                : (self ? (const void*)k_mw_knn<2, true> : (const void*)k_mw_knn<2, false>);
-        HIPC(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)klds));
-        if (three) {
-          if (self) hipLaunchKernelGGL((k_mw_knn<3, true>), dim3(wgrid), dim3(64), klds, h->stream, ka);
-          else hipLaunchKernelGGL((k_mw_knn<3, false>), dim3(wgrid), dim3(64), klds, h->stream, ka);
-        } else {
-          if (self) hipLaunchKernelGGL((k_mw_knn<2, true>), dim3(wgrid), dim3(64), klds, h->stream, ka);
-          else hipLaunchKernelGGL((k_mw_knn<2, false>), dim3(wgrid), dim3(64), klds, h->stream, ka);
-        }
-      }
-      if (h->geo)
-        hipLaunchKernelGGL(k_mw_geo_dist, dim3((unsigned)((pc * K + 255) / 256)), dim3(256), 0, h->stream, J.lon + p0, J.lat + p0, pc, K,
-                           (const double*)h->xs.as<double>(), (const double*)h->ys.as<double>(), (const int*)idx, dist);
-      MwArgs a{};
-      a.sx = h->xs.as<double>();
-      a.sy = h->ys.as<double>();
-      a.sz = h->zs.as<double>();
-      a.mode = h->geo ? 1 : h->ndim;
-      a.K = K;
-      a.npt = (int)pc;
-      a.idx = idx;
-      a.dist = dist;
-      a.Z = h->vals.as<double>();
-      a.v = h->v;
-      a.exact = h->exact;
-      a.eps = h->eps;
-      a.z = J.zs + p0;
-      a.ss = J.sss + p0;
-      a.flag = h->flag.as<int>();
-      a.nrow = 1;
-      a.zstride = h->N;
-      a.pstride = npt;
-      {  // right-hand sides in place over the distances
-        const long ne = pc * K;
-        const unsigned rg = (unsigned)((ne + 255) / 256);
-        if (custom) {
-          // d -> gamma(d) on the host for the point-station distances and for the K x K station pairs of every point
-          HIPC(hipMemcpyAsync(gvec.p, dist, sizeof(double) * ne, hipMemcpyDeviceToDevice, h->stream));
-          MIKC(custom_roundtrip(h, gvec.as<double>(), pc, K, K));
-          hipLaunchKernelGGL(k_mw_rhs_table, dim3(rg), dim3(256), 0, h->stream, dist, (const double*)gvec.as<double>(), ne, h->exact,
-                             h->eps);
-          hipLaunchKernelGGL(k_mw_pairdist, dim3((unsigned)((ne * K + 255) / 256)), dim3(256), 0, h->stream, (const int*)idx, pc, K,
-                             a.sx, a.sy, a.sz, a.mode, gtab.as<double>());
-          MIKC(custom_roundtrip(h, gtab.as<double>(), pc * K, K, K));
-          a.gtab = gtab.as<double>();
-        } else {
-          MwRhsArgs ra{};
-          ra.dist = dist, ra.n = ne, ra.v = h->v, ra.exact = h->exact, ra.eps = h->eps;
-          if (J.nd > 1) {  // block centres: the mean of the nodes' right-hand sides (the job's owner admits Euclidean named models only)
-            ra.idx = idx, ra.K = K;
-            ra.qx = qx + p0, ra.qy = qy + p0, ra.qz = three ? qz + p0 : nullptr;
-            ra.sx = a.sx, ra.sy = a.sy, ra.sz = a.sz;
-            ra.off = J.off, ra.nd = J.nd;
-            if (h->ndim == 3) { MW_RHS(3, rg, ra) } else { MW_RHS(2, rg, ra) }
-          } else {
-            MW_RHS(0, rg, ra)
-          }
-        }
-      }
-      HIPC(hipEventRecord(h->evpool[2 + 2 * solve_chunks], h->stream));
-      if (nf == 0) {
-        MIKC(solve(a, pc));
-      } else {
-        for (int f = 0; f < gn; f += rows) {  // field g0 + f .. in the rows of one pass
-          a.nrow = std::min(rows, gn - f);
-          a.Z = fv + (size_t)(g0 + f) * (size_t)h->N;
-          a.z = zpl + (size_t)f * (size_t)npt + p0;
-          MIKC(solve(a, pc));
-        }
-      }
-      HIPC(hipEventRecord(h->evpool[3 + 2 * solve_chunks], h->stream));
-      ++solve_chunks;
-      HIPC(hipGetLastError());
-    }
-    const unsigned ugrid = (unsigned)((npt + 255) / 256);
-    if (nf == 0) {
-      if (permuted)  // back to the caller's order
-        hipLaunchKernelGGL(k_ps_unsort, dim3(ugrid), dim3(256), 0, h->stream, J.perm, npt, (const double*)J.zs, (const double*)J.sss, J.z, J.ss);
-    } else {
-      if (permuted) {  // sigma^2 and the group's planes back to the caller's order, two per launch (sigma^2 again beside an odd last plane)
-        for (int q = -1; q < gn; q += 2) {
-          const double* s0 = q < 0 ? J.sss : J.fs + (size_t)q * npt;
-          double* d0 = q < 0 ? J.ss : J.fz + (size_t)q * npt;
-          const bool pair = q + 1 < gn;
-          const double* s1 = pair ? J.fs + (size_t)(q + 1) * npt : J.sss;
-          double* d1 = pair ? J.fz + (size_t)(q + 1) * npt : J.ss;
-          hipLaunchKernelGGL(k_ps_unsort, dim3(ugrid), dim3(256), 0, h->stream, J.perm, npt, s0, s1, d0, d1);
-        }
-      }
-      if (J.landing) {
-        // the group's planes leave for the landing zones behind the solves
-        HIPC(hipEventRecord(h->evpool[1], h->stream));
-        HIPC(hipStreamWaitEvent(h->stream_d2h, h->evpool[1], 0));
-        for (int f = 0; f < gn; ++f) {
-          const int fi = g0 + f;
-          double* dst = fi == 0 ? h->pin_out.as<double>() : h->pin_fz.as<double>() + (size_t)(fi - 1) * npt;
-          HIPC(hipMemcpyAsync(dst, J.fz + (size_t)f * npt, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
-        }
-        HIPC(hipEventRecord(h->ev_d2h, h->stream_d2h));
-      } else {
-        // ... or for the caller's planes, in stream order (the next group overwrites the device planes only behind these copies)
-        HIPC(hipMemcpyAsync(J.hz + (size_t)g0 * npt, J.fz, sizeof(double) * (size_t)gn * npt, hipMemcpyDeviceToHost, h->stream));
-      }
+  }
+  MwRhsArgs ra{};
+  ra.dist = dist, ra.n = ne, ra.v = h->v, ra.exact = h->exact, ra.eps = h->eps;
+  if (J.nd > 1) {  // block centres: the mean of the nodes' right-hand sides (the job's owner admits Euclidean named models only)
+    ra.idx = a.idx, ra.K = p.K;
+    ra.qx = J.qx + p0, ra.qy = J.qy + p0, ra.qz = p.three ? J.qz + p0 : nullptr;
+    ra.sx = a.sx, ra.sy = a.sy, ra.sz = a.sz;
+    ra.off = J.off, ra.nd = J.nd;
+    if (h->ndim == 3) launch_mw_rhs<3>(h, rg, ra);
+    else launch_mw_rhs<2>(h, rg, ra);
+  } else {
+    launch_mw_rhs<0>(h, rg, ra);
+  }
+  return MIK_OK;
+}
+
+// one solver pass over the chunk: a.nrow value rows from a.Z into a.z, sigma^2 into a.ss
+static int mw_solve(mik_handle* h, const MwPlan& p, MwWork& w, const MwArgs& a, long pc) {
+  const int grid = (int)std::min<long>(p.sgrid, pc);
+  switch (p.solver) {
+    case MW_BIG:
+      if (p.solve_lds > 150 * 1024) return fail(MIK_EINVAL, "n_closest_points too large for the device path (> ~7600)");
+      HIPC(hipFuncSetAttribute((const void*)k_mw_solve_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.solve_lds));
+      hipLaunchKernelGGL(k_mw_solve_big, dim3(grid), dim3(256), p.solve_lds, h->stream, a, w.sysbuf.as<double>());
+      return MIK_OK;
+    case MW_CHOLB:
+      HIPC(hipFuncSetAttribute((const void*)k_mw_chol_blocked, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.solve_lds));
+      hipLaunchKernelGGL(k_mw_chol_blocked, dim3(grid), dim3(256), p.solve_lds, h->stream, a, w.sysbuf.as<double>(), p.cslot, p.ldc);
+      return MIK_OK;
+    case MW_CHOL: return launch_mw_chol_class(h, a, pc, mw_chol_class(h, p.K));
+    default: return dispatch_mw_solve(h, a, pc);  // (always the pivoting form: valid for every window, the only one built)
+  }
+}
+
+// a group's results back in the caller's order, then its gn planes (fields g0 ..) on their way to the host
+static int mw_deliver(mik_handle* h, const MwPlan& p, const MwJob& J, int g0, int gn) {
+  const long npt = p.npt;
+  const unsigned ugrid = (unsigned)((npt + 255) / 256);
+  if (p.nf == 0) {
+    if (p.permuted)
+      hipLaunchKernelGGL(k_ps_unsort, dim3(ugrid), dim3(256), 0, h->stream, J.perm, npt, (const double*)J.zs, (const double*)J.sss, J.z, J.ss);
+    return MIK_OK;
+  }
+  if (p.permuted) {  // sigma^2 and the group's planes, two per launch (sigma^2 again beside an odd last plane)
+    for (int q = -1; q < gn; q += 2) {
+      const double* s0 = q < 0 ? J.sss : J.fs + (size_t)q * npt;
+      double* d0 = q < 0 ? J.ss : J.fz + (size_t)q * npt;
+      const bool pair = q + 1 < gn;
+      const double* s1 = pair ? J.fs + (size_t)(q + 1) * npt : J.sss;
+      double* d1 = pair ? J.fz + (size_t)(q + 1) * npt : J.ss;
+      hipLaunchKernelGGL(k_ps_unsort, dim3(ugrid), dim3(256), 0, h->stream, J.perm, npt, s0, s1, d0, d1);
     }
   }
-  int flag = 0;
-  HIPC(hipMemcpyAsync(&flag, h->flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (J.landing) {
+    // the group's planes leave for the landing zones behind the solves
+    HIPC(hipEventRecord(h->evpool[1], h->stream));
+    HIPC(hipStreamWaitEvent(h->stream_d2h, h->evpool[1], 0));
+    for (int f = 0; f < gn; ++f) {
+      const int fi = g0 + f;
+      double* dst = fi == 0 ? h->pin_out.as<double>() : h->pin_fz.as<double>() + (size_t)(fi - 1) * npt;
+      HIPC(hipMemcpyAsync(dst, J.fz + (size_t)f * npt, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
+    }
+    HIPC(hipEventRecord(h->ev_d2h, h->stream_d2h));
+  } else {
+    // ... or for the caller's planes, in stream order (the next group overwrites the device planes only behind these copies)
+    HIPC(hipMemcpyAsync(J.hz + (size_t)g0 * npt, J.fz, sizeof(double) * (size_t)gn * npt, hipMemcpyDeviceToHost, h->stream));
+  }
+  return MIK_OK;
+}
+
+// the singularity flag and the event times of a job whose `solves` chunk solves have been issued; waits for the stream
+static int mw_read_back(mik_handle* h, const MwPlan& p, long solves, int* flag) {
+  HIPC(hipMemcpyAsync(flag, h->flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPC(hipEventRecord(h->evpool[1], h->stream));
   HIPC(hipStreamSynchronize(h->stream));  // also: the scoped work buffers are released only after the stream drained
   float ms = 0.f;
   HIPC(hipEventElapsedTime(&ms, h->evpool[0], h->evpool[1]));
   h->tm.predict_ms = ms;
-  for (long c = 0; c < solve_chunks; ++c) {  // the per-point solves (the dominant kernel of this path) on their own
+  for (long c = 0; c < solves; ++c) {  // the per-point solves (the dominant kernel of this path) on their own
     HIPC(hipEventElapsedTime(&ms, h->evpool[2 + 2 * c], h->evpool[3 + 2 * c]));
     h->tm.contract_ms += ms;
   }
-  h->tm.contract_launches = solve_chunks;
-  h->tm.mw_kernel = chol ? 1 : cholb ? 4 : (big ? 3 : 2);
+  h->tm.contract_launches = solves;
+  h->tm.mw_kernel = p.solver;
   h->tm.rhs_ms = h->tm.predict_ms - h->tm.contract_ms;  // neighbour search + right-hand sides
-  if ((flag & 2) && !mw_piv) {  // a local system was not positive definite after the shift: redo with partial pivoting
+  return MIK_OK;
+}
+
+// (the caller has recorded evpool[0] on the stream and built the station grid if the search runs in LDS)
+static int run_mw_job(mik_handle* h, int K, const MwJob& J) {
+  reset_predict_timing(h);
+  MwPlan p;
+  MwWork w;
+  MIKC(plan_mw_job(h, K, J, p, w));
+  if (p.nf > 0) MIKC(mw_stage_fields(h, J));
+  MIKC(get_events(h, 2 + 2 * (size_t)p.ngroups * (size_t)p.nchunks));
+  const double* fv = h->fv.as<double>();
+  long solves = 0;
+  for (int g0 = 0; g0 < std::max(p.nf, 1); g0 += p.fg) {
+    const int gn = p.nf > 0 ? std::min(p.fg, p.nf - g0) : 0;  // fields of this group
+    double* zpl = p.permuted ? J.fs : J.fz;
+    if (g0 > 0 && J.landing) HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));  // the previous group's planes have left
+    for (long p0 = 0; p0 < p.npt; p0 += p.chunk) {
+      const long pc = std::min(p.chunk, p.npt - p0);
+      MIKC(mw_search(h, p, w, J, p0, pc));
+      MwArgs a = mw_args(h, p, J, p0, pc);
+      MIKC(mw_rhs(h, p, w, J, a, p0, pc));
+      HIPC(hipEventRecord(h->evpool[2 + 2 * solves], h->stream));
+      if (p.nf == 0) MIKC(mw_solve(h, p, w, a, pc));
+      for (int f = 0; f < gn; f += p.rows) {  // field g0 + f .. in the rows of one pass
+        a.nrow = std::min(p.rows, gn - f);
+        a.Z = fv + (size_t)(g0 + f) * (size_t)h->N;
+        a.z = zpl + (size_t)f * (size_t)p.npt + p0;
+        MIKC(mw_solve(h, p, w, a, pc));
+      }
+      HIPC(hipEventRecord(h->evpool[3 + 2 * solves], h->stream));
+      ++solves;
+      HIPC(hipGetLastError());
+    }
+    MIKC(mw_deliver(h, p, J, g0, gn));
+  }
+  int flag = 0;
+  MIKC(mw_read_back(h, p, solves, &flag));
+  if ((flag & 2) && !p.mw_piv) {  // a local system was not positive definite after the shift: redo with partial pivoting
     HIPC(hipEventRecord(h->evpool[0], h->stream));
     h->mw_force_piv = true;
     const int rc = run_mw_job(h, K, J);
@@ -509,22 +539,66 @@ static int run_mw_job(mik_handle* h, int K, const MwJob& J) {
   return MIK_OK;
 }
 
+// Small windows over a point list in no spatial order (round 4, second session): the lane-per-point search needs 64
+// consecutive points to share a few cells of the station grid.  The points are then put in Hilbert-curve order on the device
+// (k_ps_*: the sorter of the range-aware contraction), searched and solved in that order -- coordinates gathered once, z and
+// sigma^2 scattered back at the end -- so a shuffled list costs what the rows of a grid cost.  Decides whether this job is such a
+// one (*sorted) and, if so, sorts: J's queries, results and perm are then the sorted ones.  (The station grid is built.)
+static int mw_sort_points(mik_handle* h, int K, MwJob& J, bool* sorted) {
+  const long npt = h->npt;
+  *sorted = false;
+  const bool cells = (long)h->grid.nx * h->grid.ny * h->grid.nz > 1;
+  const bool coherent = h->pts_step >= 0.0 && 64.0 * h->pts_step <= 10.0 * h->grid.cell;
+  if (!(h->opt_mw_knn_lane && h->opt_sort_points != 0 && K <= 16 && cells && !h->geo && h->model != MIK_MODEL_CUSTOM && !coherent &&
+        h->pts_extent > 0.0 && npt >= 4096))
+    return MIK_OK;
+  const double spacing = h->pts_extent / std::pow((double)npt, 1.0 / h->ndim);  // of a sorted list: a wavefront's 64 points are a patch
+  if (!(12.0 * spacing <= 10.0 * h->grid.cell)) return MIK_OK;                    // ~8 spacings across
+  // (segments of 131 072 points like the contraction's launches: the bounding box and the scan of a segment are ONE workgroup
+  // each -- a single 2^20-point segment spent 0.53 + 2 x 0.39 ms in them, eight segments side by side 0.2 ms in all)
+  const long schunk = std::min<long>(((npt + 127) / 128) * 128, 131072L);
+  if (!(h->ps_valid && h->ps_chunk == schunk)) MIKC(sort_points(h, schunk, (npt + schunk - 1) / schunk));
+  const size_t nbp = sizeof(double) * (size_t)npt;
+  MIKC(h->ps_x.ensure(nbp));
+  MIKC(h->ps_y.ensure(nbp));
+  if (h->ndim == 3) MIKC(h->ps_z.ensure(nbp));
+  MIKC(h->ps_zs.ensure(nbp));
+  MIKC(h->ps_sss.ensure(nbp));
+  hipLaunchKernelGGL(k_ps_gather, dim3((unsigned)((npt + 255) / 256)), dim3(256), 0, h->stream, (const unsigned*)h->ps_idx[0].as<unsigned>(),
+                     npt, J.qx, J.qy, h->ndim == 3 ? J.qz : (const double*)nullptr, h->ps_x.as<double>(), h->ps_y.as<double>(),
+                     h->ndim == 3 ? h->ps_z.as<double>() : (double*)nullptr);
+  J.qx = h->ps_x.as<double>(), J.qy = h->ps_y.as<double>();
+  if (h->ndim == 3) J.qz = h->ps_z.as<double>();
+  J.zs = h->ps_zs.as<double>(), J.sss = h->ps_sss.as<double>();
+  J.perm = (const unsigned*)h->ps_idx[0].as<unsigned>();
+  *sorted = true;
+  return MIK_OK;
+}
+
+// blocks: sigma^2_V = (-lam . bbar - mu) - gbar: once, behind the job -- a redo with pivoting re-enters run_mw_job and must not subtract
+// twice.  Waits for the stream: the result copies run on another one, and the caller's offsets and gbar go out of scope.
+static int mw_block_epilogue(mik_handle* h, const MwJob& J, double* gbar) {
+  HIPC(hipEventRecord(h->evpool[0], h->stream));
+  MIKC(launch_block_gamma(h, J.off, J.nd, gbar));
+  MIKC(launch_block_ss(h, J.ss, J.npt, gbar));
+  HIPC(hipEventRecord(h->evpool[1], h->stream));
+  HIPC(hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPC(hipEventElapsedTime(&ms, h->evpool[0], h->evpool[1]));
+  h->tm.predict_ms += ms;
+  h->tm.rhs_ms += ms;  // (everything of the call that is not a solve)
+  return MIK_OK;
+}
+
 // The moving window over the resident points: mik_predict_moving_window (nd = 0) and mik_predict_block_window (the points are block
 // centres, offsets the nd x ndim adjusted node offsets on the host).  nd = 1 is a block of one node at its centre: the point form.
-static int predict_mw_body(mik_handle* h, int n_closest, const double* offsets, int nd, const char* name) {
-  if (!h || !h->have_problem) return fail(MIK_ESTATE, std::string(name) + ": set the problem first");
-  if (!h->have_points) return fail(MIK_ESTATE, std::string(name) + ": set points first");
-  if (h->p != 0) return fail(MIK_EINVAL, "moving-window kriging exists for ordinary kriging only (ok.py:929, ok3d.py:901)");
-  if (n_closest < 2) return fail(MIK_EINVAL, "n_closest_points has to be at least two!");
-  if (n_closest > h->N) return fail(MIK_EINVAL, "n_closest_points exceeds the number of stations");
+// The entry points have made the refusals (one_predict_mw; mik_predict_block_window, mikrige.hip).
+static int predict_mw_body(mik_handle* h, int K, const double* offsets, int nd) {
   HIPC(hipSetDevice(h->device));
   MIKC(get_events(h, 2));
   const long npt = h->npt;
-  const int K = n_closest;
   const int nf = h->nf;
-  h->tm.rhs_ms = h->tm.contract_ms = h->tm.predict_ms = 0.0;
-  h->tm.contract_launches = 0;
-  h->tm.contract_flops_executed = 0.0;
+  reset_predict_timing(h);
   h->nf_done = 0;
   if (npt == 0) {
     h->have_results = true;
@@ -533,7 +607,6 @@ static int predict_mw_body(mik_handle* h, int n_closest, const double* offsets, 
   }
   HIPC(hipStreamWaitEvent(h->stream, h->ev_d2h, 0));
   HIPC(hipEventRecord(h->evpool[0], h->stream));
-  const bool custom = h->model == MIK_MODEL_CUSTOM;
   MwJob J;
   J.npt = npt;
   J.qx = h->px.as<double>(), J.qy = h->py.as<double>(), J.qz = h->pz.as<double>();
@@ -547,40 +620,11 @@ static int predict_mw_body(mik_handle* h, int n_closest, const double* offsets, 
                        p3 + npt, p3 + 2 * (size_t)npt);
     J.qx = p3, J.qy = p3 + npt, J.qz = p3 + 2 * (size_t)npt;
   }
-  // Small windows over a point list in no spatial order (round 4, second session): the lane-per-point search needs 64
-  // consecutive points to share a few cells of the station grid.  The points are then put in Hilbert-curve order on the device
-  // (k_ps_*: the sorter of the range-aware contraction), searched and solved in that order -- coordinates gathered once, z and
-  // sigma^2 scattered back at the end -- so a shuffled list costs what the rows of a grid cost.
   bool mw_sorted = false;
   J.zs = J.z = h->z.as<double>(), J.sss = J.ss = h->ss.as<double>();
   if (mw_knn_cap(K) <= h->opt_mw_lds_cap) {
     MIKC(build_mw_grid(h, std::max(8, std::min(K, 256))));
-    const bool cells = (long)h->grid.nx * h->grid.ny * h->grid.nz > 1;
-    const bool coherent = h->pts_step >= 0.0 && 64.0 * h->pts_step <= 10.0 * h->grid.cell;
-    if (h->opt_mw_knn_lane && h->opt_sort_points != 0 && K <= 16 && cells && !h->geo && !custom && !coherent && h->pts_extent > 0.0 &&
-        npt >= 4096) {
-      const double spacing = h->pts_extent / std::pow((double)npt, 1.0 / h->ndim);  // of a sorted list: a wavefront's 64 points are a patch
-      if (12.0 * spacing <= 10.0 * h->grid.cell) {                                   // ~8 spacings across
-        // (segments of 131 072 points like the contraction's launches: the bounding box and the scan of a segment are ONE workgroup
-        // each -- a single 2^20-point segment spent 0.53 + 2 x 0.39 ms in them, eight segments side by side 0.2 ms in all)
-        const long schunk = std::min<long>(((npt + 127) / 128) * 128, 131072L);
-        if (!(h->ps_valid && h->ps_chunk == schunk)) MIKC(sort_points(h, schunk, (npt + schunk - 1) / schunk));
-        const size_t nbp = sizeof(double) * (size_t)npt;
-        MIKC(h->ps_x.ensure(nbp));
-        MIKC(h->ps_y.ensure(nbp));
-        if (h->ndim == 3) MIKC(h->ps_z.ensure(nbp));
-        MIKC(h->ps_zs.ensure(nbp));
-        MIKC(h->ps_sss.ensure(nbp));
-        hipLaunchKernelGGL(k_ps_gather, dim3((unsigned)((npt + 255) / 256)), dim3(256), 0, h->stream, (const unsigned*)h->ps_idx[0].as<unsigned>(),
-                           npt, J.qx, J.qy, h->ndim == 3 ? J.qz : (const double*)nullptr, h->ps_x.as<double>(), h->ps_y.as<double>(),
-                           h->ndim == 3 ? h->ps_z.as<double>() : (double*)nullptr);
-        J.qx = h->ps_x.as<double>(), J.qy = h->ps_y.as<double>();
-        if (h->ndim == 3) J.qz = h->ps_z.as<double>();
-        J.zs = h->ps_zs.as<double>(), J.sss = h->ps_sss.as<double>();
-        J.perm = (const unsigned*)h->ps_idx[0].as<unsigned>();
-        mw_sorted = true;
-      }
-    }
+    MIKC(mw_sort_points(h, K, J, &mw_sorted));
     J.lane = mw_sorted || (h->pts_step >= 0.0 && 64.0 * h->pts_step * (h->geo ? MIK_PI / 180.0 : 1.0) <= 10.0 * h->grid.cell);
   }
   if (nf > 0) {
@@ -601,19 +645,7 @@ static int predict_mw_body(mik_handle* h, int n_closest, const double* offsets, 
     J.off = blk.as<double>(), J.nd = nd;
   }
   MIKC(run_mw_job(h, K, J));
-  if (nd > 1) {
-    // sigma^2_V = (-lam . bbar - mu) - gbar: once, behind the job -- a redo with pivoting re-enters run_mw_job and must not subtract twice
-    double* gbar = blk.as<double>() + (size_t)nd * (size_t)h->ndim;
-    HIPC(hipEventRecord(h->evpool[0], h->stream));
-    MIKC(launch_block_gamma(h, J.off, nd, gbar));
-    MIKC(launch_block_ss(h, J.ss, npt, gbar));
-    HIPC(hipEventRecord(h->evpool[1], h->stream));
-    HIPC(hipStreamSynchronize(h->stream));  // the copies below run on another stream, and blk goes out of scope
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, h->evpool[0], h->evpool[1]));
-    h->tm.predict_ms += ms;
-    h->tm.rhs_ms += ms;  // (everything of the call that is not a solve)
-  }
+  if (nd > 1) MIKC(mw_block_epilogue(h, J, blk.as<double>() + (size_t)nd * (size_t)h->ndim));
   MIKC(h->pin_out.ensure(sizeof(double) * 2 * (size_t)npt));
   if (nf == 0) HIPC(hipMemcpyAsync(h->pin_out.as<double>(), h->z.p, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
   HIPC(hipMemcpyAsync(h->pin_out.as<double>() + npt, h->ss.p, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream_d2h));
@@ -623,11 +655,14 @@ static int predict_mw_body(mik_handle* h, int n_closest, const double* offsets, 
   return MIK_OK;
 }
 
-int one_predict_mw(mik_handle* h, int n_closest) { return predict_mw_body(h, n_closest, nullptr, 0, "mik_predict_moving_window"); }
-
-int one_predict_block_mw(mik_handle* h, const double* offsets, int nd, int n_closest) {
-  return predict_mw_body(h, n_closest, offsets, nd, "mik_predict_block_window");
+int one_predict_mw(mik_handle* h, int n_closest) {
+  if (!h || !h->have_problem) return fail(MIK_ESTATE, "mik_predict_moving_window: set the problem first");
+  if (!h->have_points) return fail(MIK_ESTATE, "mik_predict_moving_window: set points first");
+  MIKC(window_refusals(h, n_closest, true));
+  return predict_mw_body(h, n_closest, nullptr, 0);
 }
+
+int one_predict_block_mw(mik_handle* h, const double* offsets, int nd, int n_closest) { return predict_mw_body(h, n_closest, offsets, nd); }
 
 // Windowed leave-one-out cross-validation (mik_cross_validate_window): the job is the stations themselves, in the cell-sorted order the
 // search grid already holds them in (G.gx / gy / gz, G.orig) -- 64 consecutive queries share a few cells by construction, so the lane
@@ -635,8 +670,7 @@ int one_predict_block_mw(mik_handle* h, const double* offsets, int nd, int n_clo
 // window by index (KnnArgs::self).  Results land in buffers of this call (cvw) and are scattered back through orig (k_ps_unsort); the
 // resident points, h->z / h->ss, the landing zones, have_results and a resident factor are not touched.
 int one_cross_validate_window(mik_handle* h, int n_closest, double* zhat_out, double* ss_out) {
-  if (h->p != 0) return fail(MIK_EINVAL, "moving-window kriging exists for ordinary kriging only (ok.py:929, ok3d.py:901)");
-  if (n_closest < 2) return fail(MIK_EINVAL, "n_closest_points has to be at least two!");
+  MIKC(window_refusals(h, n_closest, false));  // (every station but the query: the bound on the window is this function's)
   const long N = h->N;
   const int K = n_closest;
   if (K > N - 1)

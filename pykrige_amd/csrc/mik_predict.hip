@@ -872,9 +872,7 @@ static int predict_prologue(mik_handle* h, const char* who, bool* empty) {
   if (!h || !h->have_factor) return fail(MIK_ESTATE, std::string(who) + ": factor first");
   if (!h->have_points) return fail(MIK_ESTATE, std::string(who) + ": set points first");
   HIPC(hipSetDevice(h->device));
-  h->tm.rhs_ms = h->tm.contract_ms = h->tm.predict_ms = 0.0;
-  h->tm.contract_launches = 0;
-  h->tm.contract_flops_executed = 0.0;
+  reset_predict_timing(h);
   h->tm.symmetric = h->opt_sym;
   h->tm.engine = 0;  // (the v_fma_f64 contraction left the library in round 6: tools/kernel_bench)
   h->tm.mw_kernel = 0;

@@ -1611,20 +1611,27 @@ int mik_predict_cov(mik_handle* h, double* cov_out) {
   return one_predict_cov(h, cov_out);
 }
 
+// What block kriging refuses about its nodes and the problem, in the words of entry point `who`; inverse: the blocks are kriged from the
+// resident inverse (mik_predict_block), which has to be a regular one
+static int block_refusals(const mik_handle* h, const double* offsets, int nd, const std::string& who, bool inverse) {
+  if (nd < 1 || nd > 512) return fail(MIK_EINVAL, who + ": nd = " + std::to_string(nd) + " discretisation nodes; 1 to 512 are built");
+  if (!offsets) return fail(MIK_EINVAL, who + ": no node offsets");
+  if (h->geo) return fail(MIK_EINVAL, who + ": geographic coordinates (the blocks of a lon / lat grid are not congruent)");
+  if (h->model == MIK_MODEL_CUSTOM) return fail(MIK_EINVAL, who + ": a custom variogram is evaluated on the host; block kriging is not built for it");
+  if (inverse && h->pinv) return fail(MIK_EINVAL, who + ": the block variance needs a regular inverse (pseudo_inv is set)");
+  if (h->is_kid || !h->kids.empty()) return fail(MIK_EINVAL, who + ": blocks are not kriged by a device group");
+  if (h->nf > 0 || h->gaps_any) return fail(MIK_EINVAL, who + ": value fields (mik_set_fields / mik_set_field_gaps) are set; blocks are kriged from the problem's values");
+  for (long i = 0; i < (long)nd * h->ndim; ++i)
+    if (!std::isfinite(offsets[i])) return fail(MIK_EINVAL, who + ": a node offset is not finite");
+  return MIK_OK;
+}
+
 // Block kriging of the resident points as block centres (mik_k_block.h).  Every refusal comes before anything is launched.
 int mik_predict_block(mik_handle* h, const double* offsets, int nd) {
   if (!h) return fail(MIK_ESTATE, "mik_predict_block: NULL handle");
   if (!h->have_problem) return fail(MIK_ESTATE, "mik_predict_block: set the problem first");
   if (!h->have_points) return fail(MIK_ESTATE, "mik_predict_block: set points first");
-  if (nd < 1 || nd > 512) return fail(MIK_EINVAL, "mik_predict_block: nd = " + std::to_string(nd) + " discretisation nodes; 1 to 512 are built");
-  if (!offsets) return fail(MIK_EINVAL, "mik_predict_block: no node offsets");
-  if (h->geo) return fail(MIK_EINVAL, "mik_predict_block: geographic coordinates (the blocks of a lon / lat grid are not congruent)");
-  if (h->model == MIK_MODEL_CUSTOM) return fail(MIK_EINVAL, "mik_predict_block: a custom variogram is evaluated on the host; block kriging is not built for it");
-  if (h->pinv) return fail(MIK_EINVAL, "mik_predict_block: the block variance needs a regular inverse (pseudo_inv is set)");
-  if (h->is_kid || !h->kids.empty()) return fail(MIK_EINVAL, "mik_predict_block: blocks are not kriged by a device group");
-  if (h->nf > 0 || h->gaps_any) return fail(MIK_EINVAL, "mik_predict_block: value fields (mik_set_fields / mik_set_field_gaps) are set; blocks are kriged from the problem's values");
-  for (long i = 0; i < (long)nd * h->ndim; ++i)
-    if (!std::isfinite(offsets[i])) return fail(MIK_EINVAL, "mik_predict_block: a node offset is not finite");
+  MIKC(block_refusals(h, offsets, nd, "mik_predict_block", true));
   if (!h->have_factor) MIKC(mik_factor(h));
   return one_predict_block(h, offsets, nd);
 }
@@ -1643,17 +1650,8 @@ int mik_predict_block_window(mik_handle* h, const double* offsets, int nd, int n
   if (!h) return fail(MIK_ESTATE, "mik_predict_block_window: NULL handle");
   if (!h->have_problem) return fail(MIK_ESTATE, "mik_predict_block_window: set the problem first");
   if (!h->have_points) return fail(MIK_ESTATE, "mik_predict_block_window: set points first");
-  if (nd < 1 || nd > 512) return fail(MIK_EINVAL, "mik_predict_block_window: nd = " + std::to_string(nd) + " discretisation nodes; 1 to 512 are built");
-  if (!offsets) return fail(MIK_EINVAL, "mik_predict_block_window: no node offsets");
-  if (h->geo) return fail(MIK_EINVAL, "mik_predict_block_window: geographic coordinates (the blocks of a lon / lat grid are not congruent)");
-  if (h->model == MIK_MODEL_CUSTOM) return fail(MIK_EINVAL, "mik_predict_block_window: a custom variogram is evaluated on the host; block kriging is not built for it");
-  if (h->is_kid || !h->kids.empty()) return fail(MIK_EINVAL, "mik_predict_block_window: blocks are not kriged by a device group");
-  if (h->nf > 0 || h->gaps_any) return fail(MIK_EINVAL, "mik_predict_block_window: value fields (mik_set_fields / mik_set_field_gaps) are set; blocks are kriged from the problem's values");
-  for (long i = 0; i < (long)nd * h->ndim; ++i)
-    if (!std::isfinite(offsets[i])) return fail(MIK_EINVAL, "mik_predict_block_window: a node offset is not finite");
-  if (h->p != 0) return fail(MIK_EINVAL, "moving-window kriging exists for ordinary kriging only (ok.py:929, ok3d.py:901)");
-  if (n_closest < 2) return fail(MIK_EINVAL, "n_closest_points has to be at least two!");
-  if (n_closest > h->N) return fail(MIK_EINVAL, "n_closest_points exceeds the number of stations");
+  MIKC(block_refusals(h, offsets, nd, "mik_predict_block_window", false));
+  MIKC(window_refusals(h, n_closest, true));
   MIKC(join_exchange(h));
   return one_predict_block_mw(h, offsets, nd, n_closest);
 }

@@ -13,6 +13,7 @@ and all run the same device path -- they keep only their return-type convention 
 MaskedArrays in every style, the others plain ndarrays unless style='masked').  'hip' is an explicit
 alias with the 'loop'/'C' convention.  There is no CPU path in this package.
 """
+import contextlib
 import os as _os
 import warnings
 
@@ -21,6 +22,18 @@ import numpy as np
 from . import _lib
 from . import core
 from . import variogram_models
+
+
+@contextlib.contextmanager
+def _singular_as(backend):
+    """A singular local system as the reference's backend reports it: lib/cok.pyx:176-177 ('C') raises ValueError('Singular matrix'),
+    scipy.linalg.solve (the others) LinAlgError."""
+    try:
+        yield
+    except np.linalg.LinAlgError as e:
+        if backend == "C":
+            raise ValueError("Singular matrix") from e
+        raise
 
 
 class _Cols:
@@ -338,14 +351,18 @@ class _KrigingBase:
                        getattr(self, "coordinates_type", "euclidean"))).encode())
         return d.digest()
 
+    def _factor_key_for(self, h):
+        """The key of this object's problem as factored on handle h: a changed library option (factor path, device group, ...)
+        invalidates the factor too.  None = not cacheable."""
+        key = self._problem_key()
+        return None if key is None else (key, h.option_epoch)
+
     def _upload_and_factor(self):
         """K1 + K2 on the device (inverse, or pseudo-inverse when pseudo_inv=True).  The reference re-assembles and re-inverts
         the matrix on every execute() (ok.py:898, 663); here the factored matrix stays on the device and is reused while the
         problem (stations, values, variogram, drift set-up) is unchanged -- a second execute() on new points only predicts."""
         h = self._get_handle()
-        key = self._problem_key()
-        if key is not None:
-            key = (key, h.option_epoch)  # a changed library option (factor path, device group, ...) invalidates the factor too
+        key = self._factor_key_for(h)
         if key is not None and key == getattr(self, "_factor_key", None):
             self.factor_reused = True
             return h
@@ -563,12 +580,8 @@ class _KrigingBase:
         self._set_problem(h)
         self._max_points = max(self._max_points, int(np.prod(P.shape)))
         P.load(h, self._ndim, with_extra=False)
-        try:
+        with _singular_as(backend):
             h.predict_moving_window(int(n_closest_points))
-        except np.linalg.LinAlgError as e:
-            if backend == "C":  # lib/cok.pyx:176-177 raises ValueError('Singular matrix'); scipy.linalg.solve LinAlgError
-                raise ValueError("Singular matrix") from e
-            raise
         self.last_timing = h.timing()
         return h.get_results()
 
@@ -750,12 +763,8 @@ class _KrigingBase:
             if n_closest_points is None:
                 h.predict()
             else:
-                try:
+                with _singular_as(backend):
                     h.predict_moving_window(int(n_closest_points))
-                except np.linalg.LinAlgError as e:
-                    if backend == "C":  # as _solve_moving_window
-                        raise ValueError("Singular matrix") from e
-                    raise
             self.last_timing = h.timing()
             zf = h.get_field_results()  # (before get_results: that one may take the landing zone over)
             ssf = None if gaps is None else h.get_field_sigmasq()
@@ -803,9 +812,7 @@ class _KrigingBase:
         they launch anything and factor themselves if no factor is resident."""
         h = self._get_handle()
         self._refuse_group(h, name, one_device)
-        key = self._problem_key()
-        if key is not None:
-            key = (key, h.option_epoch)
+        key = self._factor_key_for(h)
         self.factor_reused = key is not None and key == getattr(self, "_factor_key", None)
         if not self.factor_reused:
             self._set_problem(h)
@@ -975,19 +982,13 @@ class _KrigingBase:
         P = self._prepare(style, axes, None)
         h = self._get_handle()
         self._refuse_group(h, "execute_block_window", "blocks are kriged on one device")
-        key = self._problem_key()
-        if key is not None:
-            key = (key, h.option_epoch)
+        key = self._factor_key_for(h)
         if key is None or key != getattr(self, "_factor_key", None):  # (a factored problem on the handle is this object's: it stays, with its factor)
             self._set_problem(h)
         self._max_points = max(self._max_points, P.npt)
         P.load(h, self._ndim, with_extra=False)
-        try:
+        with _singular_as(backend):
             h.predict_block_window(off, k)
-        except np.linalg.LinAlgError as e:
-            if backend == "C":  # as _solve_moving_window
-                raise ValueError("Singular matrix") from e
-            raise
         self.last_timing = h.timing()
         z, ss = h.get_results()
         return self._finish(z, ss, style, P.shape, None, backend)
@@ -1118,21 +1119,15 @@ class _KrigingBase:
         if k > n - 1:
             raise ValueError("n_closest_points = %d exceeds the number of other stations (N - 1 = %d)" % (k, n - 1))
         h = self._get_handle()
-        key = self._problem_key()
-        if key is not None:
-            key = (key, h.option_epoch)
+        key = self._factor_key_for(h)
         if key is None or key != getattr(self, "_factor_key", None):  # (a factored problem on the handle is this object's: it stays, with its factor)
             self._set_problem(h)
         if v is not None:
             self._max_fields = max(self._max_fields, v.shape[1])
             h.set_fields(v.T)
         try:
-            try:
+            with _singular_as(backend):
                 zhat, ss = h.cross_validate_window(k)
-            except np.linalg.LinAlgError as e:
-                if backend == "C":  # as _solve_moving_window
-                    raise ValueError("Singular matrix") from e
-                raise
             self.last_timing = h.timing()
         finally:
             if v is not None:
