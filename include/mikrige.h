@@ -510,6 +510,33 @@ int  mik_predict_block(mik_handle *h, const double *offsets /* nd x ndim, ADJUST
  * that spans a device group, value fields or gaps being set, drift terms (ordinary kriging only), n_closest_points < 2 or > n. */
 int  mik_predict_block_window(mik_handle *h, const double *offsets /* nd x ndim, ADJUSTED */, int nd, int n_closest_points);
 
+/* Fields with missing stations through the moving window (ABI 9, added without a version step like mik_cross_validate_folds: a library
+ * without the symbol is stale).  The fields are those of mik_set_fields -- with none set, the one field is the problem's values and nf = 1 --,
+ * the points the resident ones; valid is nf x n bytes, field-major like the values, 1 = measured, and belongs to this call alone.  Plane f of
+ * z_out and of ss_out (nf x npt doubles each, the caller's point order, the caller's memory) is what mik_predict_moving_window(k) returns for
+ * the problem of the stations with valid[f] alone (same variogram, adjusted coordinates, exact_values, station order): the window of a point
+ * is its k nearest stations AMONG THOSE FIELD f HAS, ascending by (squared distance, caller's station index).  The values at missing entries
+ * are never read (they may be NaN).  No N x N matrix or inverse exists on this path: needs mik_set_problem + mik_set_points and NO factor --
+ * none is needed, built or invalidated.
+ *   Fields with the same valid column form a pattern; patterns run in order of first appearance, one moving-window job each over the
+ *   pattern's fields: one search, one set of right-hand sides, one sigma^2 (its fields share the bits of their ss_out planes), the fields in
+ *   the solver's row groups (up to G - 2 per pass of the LDL^T kernel, one per launch of the other solvers; plane f bit for bit the
+ *   one-field call).  The search of a pattern with a gap is k_mw_knn<NDIM + 4, false> (MIK_MW_LIVE, mik_k_mw.h; the lane pass, an accelerator only, is off for it): a byte
+ *   per station in the grid's cell-sorted order, n bytes uploaded per pattern, and a dead station never becomes a candidate.  A pattern
+ *   without a gap -- and valid = NULL makes every field one -- runs the unmasked kernels: its planes are mik_predict_moving_window's bit for
+ *   bit.  The lane decision, the Hilbert sort of a shuffled point list, the right-hand sides, the four solvers, the redo with pivoting (of
+ *   that one pattern) and "Singular matrix" (MIK_ESINGULAR) are mik_predict_moving_window's.  mik_timing is filled as by
+ *   mik_predict_moving_window, rhs_ms / contract_ms / predict_ms / contract_launches summed over the patterns, mw_kernel the last pattern's.
+ * MIK_EINVAL, before anything is launched: a handle that spans a device group, gaps set through mik_set_field_gaps, a custom variogram, drift
+ * terms (ordinary kriging only), n_closest_points < 2 or > n, a window beyond the neighbour search in LDS (n_closest_points + 256 >
+ * "mw_lds_cap", 7936 by default: the list scan in HBM has no masked form), and a field with fewer than n_closest_points valid stations (the
+ * message names the first).
+ * The device planes of an earlier predict (z, sigma^2, the field planes) are overwritten and mik_get_results refuses until the next predict;
+ * the resident points, a resident factor and the results of mik_cross_validate_window stay as they are.  z_out / ss_out are undefined after an
+ * error. */
+int  mik_predict_window_gaps(mik_handle *h, int n_closest_points, const uint8_t *valid /* nf x n, NULL = no gaps */,
+                             double *z_out /* nf x npt */, double *ss_out /* nf x npt */);
+
 /* Variogram-fit statistics: replaces core._find_statistics -> core._krige (core.py:759-836, 654-756): for
  * i = 1..n-1 station i is kriged from stations 0..i-1.  k_out / ss_out have n entries (entry 0 unused = 0). */
 int  mik_statistics(mik_handle *h, double *k_out, double *ss_out);

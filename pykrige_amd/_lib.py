@@ -104,6 +104,7 @@ SIGNATURES = {
     "mik_predict_block": (C.c_int, [C.c_void_p, _dp, C.c_int]),
     "mik_predict_block_window": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int]),
     "mik_predict_moving_window": (C.c_int, [C.c_void_p, C.c_int]),
+    "mik_predict_window_gaps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), _dp, _dp]),
     "mik_cross_validate": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "mik_cross_validate_folds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, _dp, _dp]),
     "mik_cross_validate_window": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
@@ -399,6 +400,23 @@ class Handle:
     def predict_moving_window(self, n_closest_points):
         self._taken = None
         check(self._lib.mik_predict_moving_window(self._h, int(n_closest_points)))
+
+    def predict_window_gaps(self, n_closest_points, valid=None):
+        """mik_predict_window_gaps: the fields of set_fields (else the problem's values) kriged at the resident points, field f from the
+        n_closest_points nearest stations among those with valid[f] (valid: (nf, n) booleans like set_field_gaps, None = no gaps).  No factor is
+        needed or touched.  Returns (z, sigma^2), both (nf, npt); the results of an earlier predict are gone (get_results refuses)."""
+        self._taken = None
+        nf = getattr(self, "_fields", None) or 1
+        m = None
+        if valid is not None:
+            m = np.ascontiguousarray(valid, dtype=np.uint8)
+            if m.shape != (nf, self._n):
+                raise ValueError("valid must have shape (%d, %d)" % (nf, self._n))
+        z = np.empty((nf, self._npt), dtype=np.float64)
+        ss = np.empty((nf, self._npt), dtype=np.float64)
+        check(self._lib.mik_predict_window_gaps(self._h, int(n_closest_points), m.ctypes.data_as(C.POINTER(C.c_uint8)) if m is not None else None,
+                                                _ptr(z), _ptr(ss)))
+        return z, ss
 
     def cross_validate(self, n_closest_points=0):
         """mik_cross_validate: station i kriged from all other stations, read off the resident inverse (n_closest_points = 0, the only form

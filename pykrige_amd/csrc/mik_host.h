@@ -534,6 +534,7 @@ int launch_block_gamma(mik_handle* h, const double* off, int nd, double* gbar); 
 int launch_block_ss(mik_handle* h, double* ss, long n, const double* gbar);                                     // mik_predict.hip: ss[0 .. n) -= gbar (k_block_ss), on h->stream
 int one_predict_mw(mik_handle* h, int n_closest);                                                               // mik_mw.hip
 int one_predict_block_mw(mik_handle* h, const double* offsets, int nd, int n_closest);                          // mik_mw.hip
+int one_predict_window_gaps(mik_handle* h, int n_closest, const uint8_t* valid, double* z_out, double* ss_out); // mik_mw.hip
 int one_cross_validate_window(mik_handle* h, int n_closest, double* zhat_out, double* ss_out);                  // mik_mw.hip
 int one_get_field_sigmasq(mik_handle* h, double* out, long ntot);                                                // mik_predict.hip
 int one_cross_validate(mik_handle* h, double* zhat_out, double* ss_out);                                         // mik_predict.hip

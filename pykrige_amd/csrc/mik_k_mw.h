@@ -38,6 +38,7 @@ struct KnnArgs {
   int npt;
   const double *gx, *gy, *gz;  // stations sorted by cell
   const int* orig;             // sorted position -> station index
+  const unsigned char* live;   // MIK_MW_LIVE forms: per sorted position 1 = the pattern has the station (one byte load beside the coordinate loads)
   const int* cstart;           // ncell + 1
   int N, K, CAP;
   int nx, ny, nz;
@@ -64,12 +65,21 @@ struct KnnArgs {
 // Reference: cKDTree.query(k) of ok.py:957-960 / ok3d.py:904-908.
 // SELF (windowed leave-one-out cross-validation, mik_cross_validate_window): query t is station a.self[t], and that one station never
 // enters the list -- left out by its INDEX, not by its distance: a second station at the same coordinates is a neighbour at distance 0.
+// Stations may be DEAD (fields with gaps through the window, mik_predict_window_gaps): NDIM = dimension + MIK_MW_LIVE instantiates the form
+// of either search in which the stations a pattern of missing values does not have are skipped by a.live.  A dead station is never a
+// candidate: it never enters a lane's list or the LDS buffer and never tightens tau (here the flag is staged through LDS with the batch,
+// folded into sid as a negative id).  The walks need no other change: a first pass whose bound holds fewer than K live stations starts again
+// without the bound, a pattern that empties a whole cluster walks more rings, and one with exactly K live stations ends on `all`.  No form
+// has both SELF and the mask.
+#define MIK_MW_LIVE 4
 template <int NDIM, int KMAX, bool SELF>
 __global__ void __launch_bounds__(64) k_mw_knn_lane(KnnArgs a) {
+  constexpr int ND = NDIM & 3;
+  constexpr bool LIVE = (NDIM & MIK_MW_LIVE) != 0;
   __shared__ double sx[64], sy[64], sz[64];
   __shared__ int sid[64];
   const int l = threadIdx.x, K = a.K;
-  constexpr int MAXCELLS = (NDIM == 3) ? 125 : 40;
+  constexpr int MAXCELLS = (ND == 3) ? 125 : 40;
   auto wmin = [](int v) {
     for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
     return v;
@@ -82,15 +92,15 @@ __global__ void __launch_bounds__(64) k_mw_knn_lane(KnnArgs a) {
     const long t = base + l;
     const bool ok = t < a.npt;
     const long ts = ok ? t : base;  // padding lanes shadow the wave's first point (they write nothing)
-    const double qx = a.px[ts], qy = a.py[ts], qz = (NDIM == 3) ? a.pz[ts] : 0.0;
+    const double qx = a.px[ts], qy = a.py[ts], qz = (ND == 3) ? a.pz[ts] : 0.0;
     int me = -1;
     if (SELF) me = a.self[ts];
     const int cx = min(a.nx - 1, max(0, (int)floor((qx - a.x0) * a.inv_cell)));
     const int cy = min(a.ny - 1, max(0, (int)floor((qy - a.y0) * a.inv_cell)));
-    const int cz = (NDIM == 3) ? min(a.nz - 1, max(0, (int)floor((qz - a.z0) * a.inv_cell))) : 0;
+    const int cz = (ND == 3) ? min(a.nz - 1, max(0, (int)floor((qz - a.z0) * a.inv_cell))) : 0;
     const int xa = max(0, wmin(cx) - 1), xb = min(a.nx - 1, wmax(cx) + 1);
     const int ya = max(0, wmin(cy) - 1), yb = min(a.ny - 1, wmax(cy) + 1);
-    const int za = (NDIM == 3) ? max(0, wmin(cz) - 1) : 0, zb = (NDIM == 3) ? min(a.nz - 1, wmax(cz) + 1) : 0;
+    const int za = (ND == 3) ? max(0, wmin(cz) - 1) : 0, zb = (ND == 3) ? min(a.nz - 1, wmax(cz) + 1) : 0;
     const long cells = (long)(xb - xa + 1) * (yb - ya + 1) * (zb - za + 1);
     bool done = false;
     double key[KMAX];
@@ -110,20 +120,20 @@ __global__ void __launch_bounds__(64) k_mw_knn_lane(KnnArgs a) {
             if (j < end) {
               sx[l] = a.gx[j];
               sy[l] = a.gy[j];
-              if (NDIM == 3) sz[l] = a.gz[j];
-              sid[l] = a.orig[j];
+              if (ND == 3) sz[l] = a.gz[j];
+              sid[l] = (LIVE && !a.live[j]) ? -1 : a.orig[j];
             }
             __syncthreads();
             const int n = min(64, end - j0);
             for (int s = 0; s < n; ++s) {
               const double dx = qx - sx[s], dy = qy - sy[s];
               double d2 = dx * dx + dy * dy;
-              if (NDIM == 3) {
+              if (ND == 3) {
                 const double dz = qz - sz[s];
                 d2 += dz * dz;
               }
               const int st = sid[s];
-              if ((!SELF || st != me) && (d2 < key[KMAX - 1] || (d2 == key[KMAX - 1] && st < id[KMAX - 1]))) {
+              if ((!SELF || st != me) && (!LIVE || st >= 0) && (d2 < key[KMAX - 1] || (d2 == key[KMAX - 1] && st < id[KMAX - 1]))) {
                 bool placed = false;
 #pragma unroll
                 for (int q = KMAX - 1; q > 0; --q) {
@@ -155,7 +165,7 @@ __global__ void __launch_bounds__(64) k_mw_knn_lane(KnnArgs a) {
       if (xb < a.nx - 1) reach = fmin(reach, (a.x0 + (xb + 1) * cell) - qx);
       if (ya > 0) reach = fmin(reach, qy - (a.y0 + ya * cell));
       if (yb < a.ny - 1) reach = fmin(reach, (a.y0 + (yb + 1) * cell) - qy);
-      if (NDIM == 3) {
+      if (ND == 3) {
         if (za > 0) reach = fmin(reach, qz - (a.z0 + za * cell));
         if (zb < a.nz - 1) reach = fmin(reach, (a.z0 + (zb + 1) * cell) - qz);
       }
@@ -182,8 +192,11 @@ __global__ void __launch_bounds__(64) k_mw_knn_lane(KnnArgs a) {
 }
 
 // SELF: as in k_mw_knn_lane -- station a.self[t] is no candidate of query t (by index), so it never reaches the buffer and never tightens tau
+// NDIM = dimension + MIK_MW_LIVE: neither does a station whose a.live byte is 0
 template <int NDIM, bool SELF>
 __global__ void __launch_bounds__(64) k_mw_knn(KnnArgs a) {
+  constexpr int ND = NDIM & 3;
+  constexpr bool LIVE = (NDIM & MIK_MW_LIVE) != 0;
   extern __shared__ double knn_lds[];
   const int K = a.K, CAP = a.CAP;
   double* keys = knn_lds;
@@ -196,7 +209,7 @@ __global__ void __launch_bounds__(64) k_mw_knn(KnnArgs a) {
   const long nwork = a.todo ? (long)*a.todo_count : (long)a.npt;
   for (long w = blockIdx.x; w < nwork; w += gridDim.x) {
     const long t = a.todo ? (long)a.todo[w] : w;
-    const double qx = a.px[t], qy = a.py[t], qz = (NDIM == 3) ? a.pz[t] : 0.0;
+    const double qx = a.px[t], qy = a.py[t], qz = (ND == 3) ? a.pz[t] : 0.0;
     int me = -1;
     if (SELF) me = a.self[t];
     int cnt = 0;
@@ -236,15 +249,18 @@ __global__ void __launch_bounds__(64) k_mw_knn(KnnArgs a) {
         // four batches of 64 stations per trip: their coordinate loads are issued together
         double d2[4];
         int id[4];
+        bool lv[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int j = j0 + u * 64 + l;
           d2[u] = 1e300;
           id[u] = 0;
+          lv[u] = true;
           if (j < end) {
+            if (LIVE) lv[u] = a.live[j] != 0;
             const double dx = qx - a.gx[j], dy = qy - a.gy[j];
             d2[u] = dx * dx + dy * dy;
-            if (NDIM == 3) {
+            if (ND == 3) {
               const double dz = qz - a.gz[j];
               d2[u] += dz * dz;
             }
@@ -253,7 +269,7 @@ __global__ void __launch_bounds__(64) k_mw_knn(KnnArgs a) {
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          const bool take = (j0 + u * 64 + l < end) && (d2[u] <= tau) && (!SELF || id[u] != me);
+          const bool take = (j0 + u * 64 + l < end) && (d2[u] <= tau) && (!SELF || id[u] != me) && (!LIVE || lv[u]);
           const unsigned long long m = __ballot(take);
           if (take) {
             const int pos = cnt + __popcll(m & below);
@@ -268,9 +284,9 @@ __global__ void __launch_bounds__(64) k_mw_knn(KnnArgs a) {
     };
     const int cx = min(a.nx - 1, max(0, (int)floor((qx - a.x0) * a.inv_cell)));
     const int cy = min(a.ny - 1, max(0, (int)floor((qy - a.y0) * a.inv_cell)));
-    const int cz = (NDIM == 3) ? min(a.nz - 1, max(0, (int)floor((qz - a.z0) * a.inv_cell))) : 0;
+    const int cz = (ND == 3) ? min(a.nz - 1, max(0, (int)floor((qz - a.z0) * a.inv_cell))) : 0;
     for (int r = 0;; ++r) {
-      const int zr = (NDIM == 3) ? r : 0;
+      const int zr = (ND == 3) ? r : 0;
       for (int dz = -zr; dz <= zr; ++dz) {
         const int z = cz + dz;
         if (z < 0 || z >= a.nz) continue;
@@ -278,7 +294,7 @@ __global__ void __launch_bounds__(64) k_mw_knn(KnnArgs a) {
           const int y = cy + dy;
           if (y < 0 || y >= a.ny) continue;
           const long row = ((long)z * a.ny + y) * a.nx;
-          const bool shell = (dy == -r || dy == r || (NDIM == 3 && (dz == -r || dz == r)));
+          const bool shell = (dy == -r || dy == r || (ND == 3 && (dz == -r || dz == r)));
           if (shell) {  // the whole row of the block is new
             const int xa = max(0, cx - r), xb = min(a.nx - 1, cx + r);
             scan(a.cstart[row + xa], a.cstart[row + xb + 1]);
@@ -289,7 +305,7 @@ __global__ void __launch_bounds__(64) k_mw_knn(KnnArgs a) {
         }
       }
       const bool all = cx - r <= 0 && cx + r >= a.nx - 1 && cy - r <= 0 && cy + r >= a.ny - 1 &&
-                       (NDIM != 3 || (cz - r <= 0 && cz + r >= a.nz - 1));
+                       (ND != 3 || (cz - r <= 0 && cz + r >= a.nz - 1));
       if (bounded && cnt < K && (r >= 1 || all)) {  // the bound was too tight here: again, without it
         bounded = false;
         cnt = 0;

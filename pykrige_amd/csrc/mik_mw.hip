@@ -175,6 +175,12 @@ struct MwJob {
   double* hz = nullptr;
   const double* off = nullptr;           // block kriging (mik_predict_block_window): the nd x ndim adjusted node offsets on the device; the
   int nd = 0;                            // queries are block centres and the right-hand sides are averaged over the nodes.  nd = 0: points
+  // a pattern of mik_predict_window_gaps: the stations the pattern has, the value rows of its fields and where their planes go
+  const unsigned char* live = nullptr;   // per SORTED station (the grid's order) 1 = the pattern has it; nullptr = every station (KnnArgs::live)
+  double live_frac = 1.0;                // the share of stations it has: scales the density behind the first-pass bound, nothing else
+  const double* fv = nullptr;            // the job's own nfl value rows (N each, caller's station order) instead of the handle's fields
+  int nfl = 0;
+  const int* fields = nullptr;           // with hz: the caller's plane of each of the job's fields (host); nullptr = plane f is field f
 };
 
 // the solver of a job's local systems; the values are timing()'s "mw_kernel"
@@ -220,7 +226,7 @@ static int size_mw_work(mik_handle* h, const MwPlan& p, const MwJob& J, MwWork& 
   }
   w.sx = h->xs.as<double>(), w.sy = h->ys.as<double>(), w.sz = h->zs.as<double>();
   if (!p.wave_knn) {
-    if (J.self) return fail(MIK_EINVAL, "moving window: the list search in HBM leaves no station out");  // (mik_cross_validate_window refuses such a K)
+    if (J.self || J.live) return fail(MIK_EINVAL, "moving window: the list search in HBM leaves no station out");  // (the entry points refuse such a K)
     MIKC(w.wd.ensure(sizeof(double) * ck));
     MIKC(w.wi.ensure(sizeof(int) * ck));
     if (h->geo) {  // station unit vectors for the plain scan
@@ -240,7 +246,7 @@ static int size_mw_work(mik_handle* h, const MwPlan& p, const MwJob& J, MwWork& 
 static int plan_mw_job(mik_handle* h, int K, const MwJob& J, MwPlan& p, MwWork& w) {
   const long npt = J.npt;
   p = MwPlan{};
-  p.K = K, p.nb = K + 1, p.nf = h->nf, p.npt = npt;
+  p.K = K, p.nb = K + 1, p.nf = J.fv ? J.nfl : h->nf, p.npt = npt;
   p.custom = h->model == MIK_MODEL_CUSTOM, p.three = h->geo || h->ndim == 3, p.permuted = J.perm != nullptr;
   // The reference cuts each point's system out of a_all = self._get_kriging_matrix(n); here its entries are computed from the selected
   // stations' coordinates, so no N x N matrix exists on this path (and a factor held by the handle stays valid).
@@ -264,7 +270,7 @@ static int plan_mw_job(mik_handle* h, int K, const MwJob& J, MwPlan& p, MwWork& 
   // one same-address atomic per wavefront, +0.3 ms -- hence K <= 16 and the coherence test: 64 consecutive points must span
   // few cells, judged by the job's owner -- one_predict_mw from the median step between consecutive points that mik_set_points /
   // mik_set_grid recorded; the cell-sorted stations of the cross-validation job are coherent by construction)
-  p.lane = p.wave_knn && h->opt_mw_knn_lane && K <= 16 && (long)h->grid.nx * h->grid.ny * h->grid.nz > 1 && J.lane;
+  p.lane = p.wave_knn && h->opt_mw_knn_lane && K <= 16 && (long)h->grid.nx * h->grid.ny * h->grid.nz > 1 && J.lane && !J.live;
   if (p.solver == MW_CHOLB) {
     p.ldc = ((K + MIK_MWP - 1) / MIK_MWP) * MIK_MWP;
     p.cslot = (long)(p.ldc + MIK_MWP) * p.ldc + 3L * K;
@@ -294,7 +300,7 @@ static int plan_mw_job(mik_handle* h, int K, const MwJob& J, MwPlan& p, MwWork& 
 
 // the value fields on the device and, for a job that delivers to them, the landing zones in the size of this job
 static int mw_stage_fields(mik_handle* h, const MwJob& J) {
-  MIKC(upload_fields(h, 0));  // the caller's station order: the neighbour lists hold the caller's station indices
+  if (!J.fv) MIKC(upload_fields(h, 0));  // the caller's station order: the neighbour lists hold the caller's station indices
   if (J.landing) {
     HIPC(hipEventSynchronize(h->ev_d2h));  // an earlier predict's copies may still write the landing zones
     MIKC(h->pin_out.ensure(sizeof(double) * 2 * (size_t)J.npt));
@@ -330,14 +336,18 @@ static KnnArgs knn_args(mik_handle* h, const MwPlan& p, const MwJob& J, long p0,
   if (h->opt_mw_knn_bound && !h->geo && G.live >= 2 && (long)G.nx * G.ny * G.nz > 1) {
     // radius of the disc / ball expected to hold K + 4 sqrt(K) + 2 of the ~per_cell stations a cell holds; it must stay
     // inside the 3 x 3 (x 3) cells around the point's cell
-    const double m = p.K + 4.0 * std::sqrt((double)p.K) + 2.0, T = std::max(1.0, G.per_cell);
+    const double m = p.K + 4.0 * std::sqrt((double)p.K) + 2.0, T = std::max(1.0, G.per_cell * J.live_frac);
     const double r2 = G.live == 3 ? std::pow(m / (4.18879020478639 * T), 2.0 / 3.0) : m / (3.14159265358979 * T);
     if (r2 <= 1.0) ka.tau0 = r2 * ka.cell2;
   }
   ka.idx_out = h->mw_idx.as<int>(), ka.dist_out = h->mw_dist.as<double>();
   if (J.self) ka.self = J.self + p0;
+  ka.live = J.live;
   return ka;
 }
+
+// host code of the calls that are not hot is built for size: the library has a size bar (tests/test_abi_and_host.py)
+#define MIK_SMALL __attribute__((minsize, noinline))
 
 // the search over the station grid in NDIM dimensions, SELF: with the query's own station left out.  Small windows: one lane per point
 // over the box of cells its wavefront's 64 consecutive points share (k_mw_knn_lane); the wave-per-point kernel then only walks the list
@@ -357,6 +367,16 @@ static int mw_search_grid(mik_handle* h, const MwPlan& p, MwWork& w, KnnArgs ka,
   return MIK_OK;
 }
 
+// ... and under a pattern's mask (ka.live): the wave-per-point kernel takes every point.  The lane pass is only an accelerator and has no
+// masked form in the library (its two forms did not fit under the library's size bar beside the entry point): plan_mw_job leaves
+// p.lane off for a masked job
+MIK_SMALL static int mw_search_live(mik_handle* h, const MwPlan& p, const KnnArgs& ka, long pc) {
+  void (*const wave)(KnnArgs) = p.three ? k_mw_knn<3 + MIK_MW_LIVE, false> : k_mw_knn<2 + MIK_MW_LIVE, false>;
+  HIPC(hipFuncSetAttribute((const void*)wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.knn_lds));
+  hipLaunchKernelGGL(wave, dim3((unsigned)std::min<long>(pc, 32L * h->n_cu)), dim3(64), p.knn_lds, h->stream, ka);
+  return MIK_OK;
+}
+
 // the K nearest stations of queries [p0, p0 + pc) into mw_idx / mw_dist: the list scan in HBM, or the searches over the station grid;
 // geographic: the chord lengths the search ordered by become great-circle distances
 static int mw_search(mik_handle* h, const MwPlan& p, MwWork& w, const MwJob& J, long p0, long pc) {
@@ -368,7 +388,8 @@ static int mw_search(mik_handle* h, const MwPlan& p, MwWork& w, const MwJob& J, 
                        h->N, p.K, w.wd.as<double>(), w.wi.as<int>(), idx, dist);
   } else {
     const KnnArgs ka = knn_args(h, p, J, p0, pc);
-    if (p.three) MIKC((J.self ? mw_search_grid<3, true>(h, p, w, ka, pc) : mw_search_grid<3, false>(h, p, w, ka, pc)));
+    if (J.live) MIKC(mw_search_live(h, p, ka, pc));
+    else if (p.three) MIKC((J.self ? mw_search_grid<3, true>(h, p, w, ka, pc) : mw_search_grid<3, false>(h, p, w, ka, pc)));
     else MIKC((J.self ? mw_search_grid<2, true>(h, p, w, ka, pc) : mw_search_grid<2, false>(h, p, w, ka, pc)));
   }
   if (h->geo)
@@ -470,7 +491,9 @@ static int mw_deliver(mik_handle* h, const MwPlan& p, const MwJob& J, int g0, in
     HIPC(hipEventRecord(h->ev_d2h, h->stream_d2h));
   } else {
     // ... or for the caller's planes, in stream order (the next group overwrites the device planes only behind these copies)
-    HIPC(hipMemcpyAsync(J.hz + (size_t)g0 * npt, J.fz, sizeof(double) * (size_t)gn * npt, hipMemcpyDeviceToHost, h->stream));
+    if (!J.fields) HIPC(hipMemcpyAsync(J.hz + (size_t)g0 * npt, J.fz, sizeof(double) * (size_t)gn * npt, hipMemcpyDeviceToHost, h->stream));
+    for (int f = 0; J.fields && f < gn; ++f)
+      HIPC(hipMemcpyAsync(J.hz + (size_t)J.fields[g0 + f] * npt, J.fz + (size_t)f * npt, sizeof(double) * npt, hipMemcpyDeviceToHost, h->stream));
   }
   return MIK_OK;
 }
@@ -501,7 +524,7 @@ static int run_mw_job(mik_handle* h, int K, const MwJob& J) {
   MIKC(plan_mw_job(h, K, J, p, w));
   if (p.nf > 0) MIKC(mw_stage_fields(h, J));
   MIKC(get_events(h, 2 + 2 * (size_t)p.ngroups * (size_t)p.nchunks));
-  const double* fv = h->fv.as<double>();
+  const double* fv = J.fv ? J.fv : h->fv.as<double>();
   long solves = 0;
   for (int g0 = 0; g0 < std::max(p.nf, 1); g0 += p.fg) {
     const int gn = p.nf > 0 ? std::min(p.fg, p.nf - g0) : 0;  // fields of this group
@@ -590,16 +613,86 @@ static int mw_block_epilogue(mik_handle* h, const MwJob& J, double* gbar) {
   return MIK_OK;
 }
 
+// Fields with gaps through the window (mik_predict_window_gaps): what the caller handed over, and the loop over patterns around the job.
+struct MwGaps {
+  const uint8_t* valid;  // nf x N in the caller's station order, 1 = measured; nullptr = no gaps
+  double *z_out, *ss_out;  // nf x npt each, caller's memory
+};
+
+// Fields with the same valid column form a pattern; patterns in order of first appearance, each with its fields in order.  A pattern shares
+// one search, one set of right-hand sides and one sigma^2: run_mw_job once per pattern over that pattern's value rows (J.fv: the rows of
+// the pattern side by side, so its fields take the solver's row groups as the fields of mik_predict_moving_window do), with the byte mask of
+// the pattern in the grid's station order (J.live; a pattern without a gap has none and runs the unmasked searches).  The redo with pivoting
+// happens inside run_mw_job: it redoes that one pattern.  Times are summed over the patterns.  (J is the job of the resident points as
+// predict_mw_body set it up: queries, order, planes of J.fg fields.)
+MIK_SMALL static int run_mw_gaps(mik_handle* h, int K, MwJob J, const MwGaps& gp) {
+  auto copy = [](void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDefault); };
+  const size_t N = (size_t)h->N, npt = (size_t)J.npt;
+  const int nf = std::max(h->nf, 1);
+  std::vector<int> iw(2 * (size_t)nf + (gp.valid ? N : 0));
+  int *pat = iw.data(), *fl = pat + nf, *orig = fl + nf;  // field -> pattern; the first fields while grouping, then a pattern's fields; G.orig
+  int npat = 0;
+  for (int f = 0; f < nf; ++f) {
+    int q = 0;
+    while (gp.valid && q < npat && memcmp(gp.valid + f * N, gp.valid + fl[q] * N, N)) ++q;
+    if (q == npat) fl[npat++] = f;
+    pat[f] = q;
+  }
+  DevBuf rows, live;
+  std::vector<unsigned char> lv(gp.valid ? N : 0);
+  if (h->nf > 0) MIKC(rows.ensure(sizeof(double) * nf * N));
+  if (gp.valid) {
+    MIKC(live.ensure(N));
+    HIPC(copy(orig, h->grid.orig.p, sizeof(int) * N));
+  }
+  J.landing = false;
+  J.hz = gp.z_out;
+  J.fields = fl;
+  double ms[3] = {0.0, 0.0, 0.0};
+  long launches = 0;
+  for (int q = 0, r0 = 0; q < npat; ++q, r0 += J.nfl) {
+    J.nfl = 0;
+    for (int f = 0; f < nf; ++f)
+      if (pat[f] == q) fl[J.nfl++] = f;
+    // the pattern's value rows side by side, and its byte mask in the grid's station order
+    J.fv = h->nf > 0 ? rows.as<double>() + r0 * N : h->vals.as<double>();
+    for (int i = 0; h->nf > 0 && i < J.nfl; ++i)
+      HIPC(copy(const_cast<double*>(J.fv) + i * N, &h->hfields[fl[i] * N], sizeof(double) * N));
+    size_t have = N;
+    if (gp.valid) {
+      const uint8_t* col = gp.valid + fl[0] * N;
+      have = 0;
+      for (size_t j = 0; j < N; ++j) have += (lv[j] = col[orig[j]] != 0);
+    }
+    J.live = nullptr, J.live_frac = 1.0;
+    if (have < N) {
+      HIPC(copy(live.p, lv.data(), N));
+      J.live = live.as<unsigned char>(), J.live_frac = (double)have / (double)N;
+    }
+    HIPC(hipEventRecord(h->evpool[0], h->stream));
+    MIKC(run_mw_job(h, K, J));
+    double* ss0 = gp.ss_out + fl[0] * npt;
+    HIPC(copy(ss0, J.ss, sizeof(double) * npt));
+    for (int i = 1; i < J.nfl; ++i) memcpy(gp.ss_out + fl[i] * npt, ss0, sizeof(double) * npt);
+    ms[0] += h->tm.rhs_ms, ms[1] += h->tm.contract_ms, ms[2] += h->tm.predict_ms, launches += h->tm.contract_launches;
+  }
+  h->tm.rhs_ms = ms[0], h->tm.contract_ms = ms[1], h->tm.predict_ms = ms[2], h->tm.contract_launches = launches;
+  return MIK_OK;
+}
+
 // The moving window over the resident points: mik_predict_moving_window (nd = 0) and mik_predict_block_window (the points are block
 // centres, offsets the nd x ndim adjusted node offsets on the host).  nd = 1 is a block of one node at its centre: the point form.
-// The entry points have made the refusals (one_predict_mw; mik_predict_block_window, mikrige.hip).
-static int predict_mw_body(mik_handle* h, int K, const double* offsets, int nd) {
+// gaps (mik_predict_window_gaps): the same job once per pattern, results to the caller's planes instead of the landing zones.
+// The entry points have made the refusals (one_predict_mw, one_predict_window_gaps; mik_predict_block_window, mikrige.hip).
+static int predict_mw_body(mik_handle* h, int K, const double* offsets, int nd, const MwGaps* gaps = nullptr) {
   HIPC(hipSetDevice(h->device));
   MIKC(get_events(h, 2));
   const long npt = h->npt;
-  const int nf = h->nf;
+  const int nf = gaps ? std::max(h->nf, 1) : h->nf;
   reset_predict_timing(h);
   h->nf_done = 0;
+  if (gaps) h->have_results = false;  // z / ss on the device become the last pattern's; nothing reaches the landing zones
+  if (npt == 0 && gaps) return MIK_OK;
   if (npt == 0) {
     h->have_results = true;
     h->nf_done = nf;
@@ -644,6 +737,7 @@ static int predict_mw_body(mik_handle* h, int K, const double* offsets, int nd) 
     HIPC(hipMemcpy(blk.p, offsets, sizeof(double) * noff, hipMemcpyHostToDevice));
     J.off = blk.as<double>(), J.nd = nd;
   }
+  if (gaps) return run_mw_gaps(h, K, J, *gaps);
   MIKC(run_mw_job(h, K, J));
   if (nd > 1) MIKC(mw_block_epilogue(h, J, blk.as<double>() + (size_t)nd * (size_t)h->ndim));
   MIKC(h->pin_out.ensure(sizeof(double) * 2 * (size_t)npt));
@@ -663,6 +757,27 @@ int one_predict_mw(mik_handle* h, int n_closest) {
 }
 
 int one_predict_block_mw(mik_handle* h, const double* offsets, int nd, int n_closest) { return predict_mw_body(h, n_closest, offsets, nd); }
+
+// mik_predict_window_gaps: the refusals that need the window -- all before anything is launched -- then the job per pattern
+MIK_SMALL int one_predict_window_gaps(mik_handle* h, int K, const uint8_t* valid, double* z_out, double* ss_out) {
+  MIKC(window_refusals(h, K, true));
+  char msg[200];
+  if (mw_knn_cap(K) > h->opt_mw_lds_cap) {
+    snprintf(msg, sizeof msg, "mik_predict_window_gaps: a window of %d stations is beyond the neighbour search in LDS (\"mw_lds_cap\" %d: n_closest_points <= %d)",
+             K, h->opt_mw_lds_cap, h->opt_mw_lds_cap - 256);
+    return fail(MIK_EINVAL, msg);
+  }
+  for (int f = 0; valid && f < std::max(h->nf, 1); ++f) {
+    long have = 0;
+    for (long i = 0; i < h->N; ++i) have += valid[(size_t)f * h->N + i] != 0;
+    if (have < K) {
+      snprintf(msg, sizeof msg, "mik_predict_window_gaps: field %d has %ld valid stations, fewer than n_closest_points = %d", f, have, K);
+      return fail(MIK_EINVAL, msg);
+    }
+  }
+  const MwGaps gp{valid, z_out, ss_out};
+  return predict_mw_body(h, K, nullptr, 0, &gp);
+}
 
 // Windowed leave-one-out cross-validation (mik_cross_validate_window): the job is the stations themselves, in the cell-sorted order the
 // search grid already holds them in (G.gx / gy / gz, G.orig) -- 64 consecutive queries share a few cells by construction, so the lane

@@ -1644,6 +1644,19 @@ int mik_predict_moving_window(mik_handle* h, int n_closest) {
   return for_each_device(h, [n_closest](int, mik_handle* d) { return one_predict_mw(d, n_closest); });
 }
 
+// Fields with gaps through the moving window: no factor is needed, built or invalidated (one_predict_window_gaps, mik_mw.hip).
+__attribute__((minsize)) int mik_predict_window_gaps(mik_handle* h, int n_closest, const uint8_t* valid, double* z_out, double* ss_out) {
+  const char* why = nullptr;
+  if (!h || !z_out || !ss_out) why = "mik_predict_window_gaps: NULL argument";
+  else if (!h->have_problem || !h->have_points) why = "mik_predict_window_gaps: set the problem and the points first";
+  else if (!h->kids.empty()) why = "mik_predict_window_gaps: not for a handle that spans a device group";
+  else if (h->gaps_any) why = "mik_predict_window_gaps: gaps set by mik_set_field_gaps belong to mik_predict; this call takes its own valid";
+  else if (h->model == MIK_MODEL_CUSTOM) why = "mik_predict_window_gaps: not built for a custom variogram";
+  if (why) return fail(h && z_out && ss_out && !(h->have_problem && h->have_points) ? MIK_ESTATE : MIK_EINVAL, why);
+  MIKC(join_exchange(h));
+  return one_predict_window_gaps(h, n_closest, valid, z_out, ss_out);
+}
+
 // Block kriging through the moving window: mik_predict_block's refusals without pseudo_inv (no inverse on this path) and the moving window's;
 // no factor is needed, built or invalidated (one_predict_block_mw, mik_mw.hip).
 int mik_predict_block_window(mik_handle* h, const double* offsets, int nd, int n_closest) {

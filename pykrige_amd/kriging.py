@@ -694,8 +694,9 @@ class _KrigingBase:
         ``ValueError`` (the identity needs a regular inverse), ``n_closest_points`` together with ``valid`` raises
         ``NotImplementedError``, and a handle that spans a device group raises ``ValueError``."""
 
-    def _field_gaps(self, values, v, valid):
-        """valid of execute_fields against the (N, F) values v: the (N, F) boolean array; v gets 0.0 where it is False."""
+    def _field_gaps(self, values, v, valid, zero=True):
+        """valid of execute_fields against the (N, F) values v: the (N, F) boolean array; v gets 0.0 where it is False (zero=False: v stays
+        as it is and a field may be empty -- execute_fields_window, whose device path never reads those entries and has a bound of its own)."""
         m = np.asarray(valid)
         if m.dtype != np.bool_:
             raise ValueError("valid must be a boolean array (True = measured); got dtype %s" % m.dtype)
@@ -705,6 +706,8 @@ class _KrigingBase:
         m = m.reshape(v.shape)
         if not np.all(np.isfinite(v[m])):
             raise ValueError("values holds non-finite entries where valid is True")
+        if not zero:
+            return m
         empty = np.flatnonzero(~m.any(axis=0))
         if empty.size:
             raise ValueError("valid: field %d has no valid station" % int(empty[0]))
@@ -993,6 +996,84 @@ class _KrigingBase:
         z, ss = h.get_results()
         return self._finish(z, ss, style, P.shape, None, backend)
 
+    # ---------------------------------------------------------------- fields with gaps through the moving window (mik_predict_window_gaps)
+    _FIELDS_WINDOW_DOC = """Krige F value fields with missing stations through the moving window.
+
+        ``zvalues, sigmasq = obj.execute_fields_window(style, xpoints, ypoints[, zpoints], values, n_closest_points, valid=None,
+        backend="loop")``
+
+        ``values`` is ``(N, F)`` or ``(N,)`` (F = 1) as in ``execute_fields()``.  ``valid`` is a boolean array of the shape of ``values``
+        and True means "measured"; it follows the rules of ``execute_fields()``'s ``valid``: boolean dtype only, entries of ``values``
+        where it is False are ignored (they may be NaN or inf and are never read), entries where it is True must be finite.
+        ``style`` is ``'points'`` or ``'grid'``.  Both outputs are plain float64 arrays of shape ``(F,) + shape``, ``shape`` being what
+        ``execute()`` returns for the same points: every field has its own sigma^2.
+
+        ``zvalues[f]`` and ``sigmasq[f]`` are what an object built from the stations with ``valid[:, f]`` alone returns from
+        ``execute(style, ..., n_closest_points=k)`` -- an object with this object's variogram parameters, anisotropy, centre,
+        ``exact_values`` and adjusted coordinates.  The window of a point is its k nearest stations among those field f has, ascending
+        by (distance, station index in the order the stations were given in).  No kriging matrix of all stations is formed or inverted:
+        the call serves station sets that have no N x N inverse, and ``pseudo_inv`` plays no part.
+
+        Fields with the same ``valid`` column form a pattern.  A pattern shares one neighbour search, one set of right-hand sides and one
+        sigma^2 (its fields share the bits of their ``sigmasq`` planes); its fields go through the local solver in row groups, up to
+        G - 2 per pass for windows up to 256 as in ``execute_fields(..., n_closest_points=k)``, and plane f is bit for bit the one-field
+        call with that column.  P distinct patterns therefore cost about P one-field window calls, one shared pattern about one
+        multi-field call.  A pattern without a gap runs the search of ``execute()``: its planes are bit for bit those of
+        ``execute_fields(..., n_closest_points=k)``; ``valid=None`` makes every field such a pattern.
+
+        ``n_closest_points`` and ``backend`` follow the moving window of ``execute()``: ``OrdinaryKriging`` and ``OrdinaryKriging3D``
+        take ``backend='loop'`` (and ``'C'`` in 2-D; all run the same device path); the universal-kriging classes have no moving window
+        and raise ``ValueError``.  ``style='masked'`` and any unknown style raise ``ValueError``; ``n_closest_points <= 1`` raises
+        ``ValueError``; a field with fewer than ``n_closest_points`` valid stations raises ``ValueError`` naming the first such field; a
+        window beyond the device's neighbour search in on-chip memory (more than 7936 stations by default) raises ``ValueError``; a
+        handle that spans a device group raises ``ValueError``; ``variogram_model='custom'`` raises ``NotImplementedError``.  A singular
+        local system raises as in ``execute()``.  ``last_timing`` is set, its times summed over the patterns.
+
+        No factor is needed, built or invalidated: a factor that ``execute()`` left on the device is neither used nor lost.  The points
+        are set as by any ``execute()``, and the device planes of an earlier ``execute()`` / ``execute_fields()`` are overwritten (arrays
+        those calls returned are the caller's and stay).  ``cross_validate_window()`` keeps its results in buffers of its own, and so do
+        ``cross_validate()``, ``execute_cov()`` and the gap planes of ``execute_fields(..., valid=)``, which every such call writes anew:
+        all of them return after this call the bits they returned before.  ``execute_fields(..., n_closest_points=, valid=)`` still
+        raises ``NotImplementedError``: this call is the moving window with gaps."""
+
+    def _execute_fields_window(self, style, axes, values, n_closest_points, valid, backend):
+        """execute_fields_window of the four classes: every argument is checked on the host before the device is touched."""
+        if style == "masked":
+            raise ValueError("execute_fields_window: style 'masked' is not built; pass the unmasked points as style 'points'")
+        if style != "grid" and style != "points":
+            raise ValueError("style argument must be 'grid' or 'points'")
+        if n_closest_points is None:
+            raise ValueError("execute_fields_window needs n_closest_points (the global form is execute_fields(..., valid=))")
+        self._check_backend(backend, n_closest_points)
+        self._refuse_custom_and_pinv("execute_fields_window", "the moving window with gaps is not built for it", None)
+        v = self._field_values(values, valid)
+        gaps = None if valid is None else self._field_gaps(values, v, valid, zero=False)
+        k = int(n_closest_points)
+        have = gaps.sum(axis=0) if gaps is not None else np.full(v.shape[1], v.shape[0])
+        short = np.flatnonzero(have < k)
+        if short.size:
+            raise ValueError("execute_fields_window: field %d has %d valid stations, fewer than n_closest_points = %d"
+                             % (int(short[0]), int(have[short[0]]), k))
+        self._refuse_group(self._handle, "execute_fields_window", "fields with gaps are kriged on one device")
+        P = self._prepare(style, axes, None)
+        h = self._get_handle()
+        self._refuse_group(h, "execute_fields_window", "fields with gaps are kriged on one device")
+        key = self._factor_key_for(h)
+        if key is None or key != getattr(self, "_factor_key", None):  # (a factored problem on the handle is this object's: it stays, with its factor)
+            self._set_problem(h)
+        self._max_points = max(self._max_points, P.npt)
+        self._max_fields = max(self._max_fields, v.shape[1])
+        P.load(h, self._ndim, with_extra=False)
+        h.set_fields(v.T)
+        try:
+            with _singular_as(backend):
+                zf, ssf = h.predict_window_gaps(k, None if gaps is None else gaps.T)
+            self.last_timing = h.timing()
+        finally:
+            h.set_fields(None)
+        nf = v.shape[1]
+        return zf.reshape((nf,) + tuple(P.shape)), ssf.reshape((nf,) + tuple(P.shape))
+
     # ---------------------------------------------------------------- leave-one-out cross-validation (mik_cross_validate)
     _CV_DOC = """Leave-one-out cross-validation on the device: every station kriged from the other stations.
 
@@ -1260,6 +1341,11 @@ class OrdinaryKriging(_KrigingBase):
         return self._execute_block(style, (xpoints, ypoints), block_size, n_disc, backend)
 
     execute_block.__doc__ = _KrigingBase._BLOCK_DOC
+
+    def execute_fields_window(self, style, xpoints, ypoints, values, n_closest_points, valid=None, backend="loop"):
+        return self._execute_fields_window(style, [xpoints, ypoints], values, n_closest_points, valid, backend)
+
+    execute_fields_window.__doc__ = _KrigingBase._FIELDS_WINDOW_DOC
 
     def execute_block_window(self, style, xpoints, ypoints, block_size, n_closest_points, n_disc=4, backend="loop"):
         return self._execute_block_window(style, (xpoints, ypoints), block_size, n_closest_points, n_disc, backend)
@@ -1529,6 +1615,11 @@ class OrdinaryKriging3D(_KrigingBase):
         return self._execute_block(style, (xpoints, ypoints, zpoints), block_size, n_disc, backend)
 
     execute_block.__doc__ = _KrigingBase._BLOCK_DOC
+
+    def execute_fields_window(self, style, xpoints, ypoints, zpoints, values, n_closest_points, valid=None, backend="loop"):
+        return self._execute_fields_window(style, [xpoints, ypoints, zpoints], values, n_closest_points, valid, backend)
+
+    execute_fields_window.__doc__ = _KrigingBase._FIELDS_WINDOW_DOC
 
     def execute_block_window(self, style, xpoints, ypoints, zpoints, block_size, n_closest_points, n_disc=4, backend="loop"):
         return self._execute_block_window(style, (xpoints, ypoints, zpoints), block_size, n_closest_points, n_disc, backend)
