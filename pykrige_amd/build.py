@@ -1,4 +1,4 @@
-"""Builds pykrige_amd/libmikrige.so (HIP, gfx950) in-tree.  `python -m pykrige_amd.build [--force] [-j N]`.
+"""Builds pykrige_amd/libmikrige.so and pykrige_amd/libmikvario.so (HIP, gfx950) in-tree.  `python -m pykrige_amd.build [--force] [-j N]`.
 
 The library is ten translation units compiled in parallel (objects under pykrige_amd/csrc/build/, git- and gpurun-ignored) and
 linked into one shared object; only the units whose sources or flags changed are recompiled (the command line of every object is
@@ -11,6 +11,10 @@ the whole build holds an flock on csrc/build/.lock, and objects / the library ar
     mik_mw.hip        moving window: neighbour search, blocked / HBM solvers, dispatch
     mik_mw_solve.hip  moving window: the register classes of the pivoting Gauss-Jordan solver (the LDL^T kernels' fallback)
     mik_mw_chol.hip   x 5 (-DMIK_MWC_PART=0..4): the register-tile classes of the moving window's LDL^T solver
+
+libmikvario.so (include/mikvario.h: directional semivariograms and variogram maps) is a second library of one unit, mik_vario.hip, built
+after the first with the same flags under the same lock and rename discipline.  It exists because libmikrige.so is held to a size bar and
+a frozen kernel list (tests/test_abi_and_host.py): new device features go here.  Nothing of it is linked into libmikrige.so or the reverse.
 """
 import os
 import shutil
@@ -23,7 +27,9 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 OUT = os.path.join(HERE, "libmikrige.so")
+OUT_VARIO = os.path.join(HERE, "libmikvario.so")
 API = os.path.join(ROOT, "include", "mikrige.h")
+API_VARIO = os.path.join(ROOT, "include", "mikvario.h")
 COMMON = ["mik_host.h", "mik_dev.h"]
 # object name -> (source, extra headers it includes, extra flags)
 UNITS = {
@@ -38,6 +44,8 @@ UNITS = {
     "mik_mw_chol3": ("mik_mw_chol.hip", ["mik_k_mw_chol.h"], ["-DMIK_MWC_PART=3"]),
     "mik_mw_chol4": ("mik_mw_chol.hip", ["mik_k_mw_chol.h"], ["-DMIK_MWC_PART=4"]),
 }
+# the second library: object name -> (source, headers it includes); its own headers only, so a change of the first library's leaves it alone
+UNITS_VARIO = {"mik_vario": ("mik_vario.hip", ["mik_k_vario.h"])}
 # --offload-compress: the code objects travel zstd-compressed inside the fat binary (16.9 -> 2.3 MB of .so; the HIP runtime unpacks them at load);
 # level 19 instead of the default 3 takes another 3 % off and no measurable compile time (the time is in code generation)
 COMPRESS = ["--offload-compress", "--offload-compression-level=19"]
@@ -81,12 +89,18 @@ def _stale(target, deps, flags=None):
     return False
 
 
+def vario_deps(name):
+    src, hdrs = UNITS_VARIO[name]
+    return [os.path.join(CSRC, f) for f in [src] + hdrs] + [API_VARIO]
+
+
 def up_to_date():
-    return not _stale(OUT, all_sources())
+    return not _stale(OUT, all_sources()) and not _stale(OUT_VARIO, [d for n in UNITS_VARIO for d in vario_deps(n)])
 
 
 def build_library(force=False, verbose=False, jobs=None):
-    """Compile the C-ABI library for gfx950.  Cross-compiles without a GPU."""
+    """Compile the two C-ABI libraries for gfx950; returns the path of libmikrige.so (OUT; libmikvario.so is OUT_VARIO).
+    Cross-compiles without a GPU."""
     if not force and up_to_date():
         return OUT
     os.makedirs(OBJ, exist_ok=True)
@@ -108,6 +122,12 @@ def _build_locked(force, verbose, jobs):
         flags = FLAGS + extra
         if force or _stale(obj, unit_deps(name), flags):
             todo.append((name, flags, [cc] + flags + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
+    relink = bool(todo) or not os.path.exists(OUT)
+    todo_vario = []
+    for name, (src, _) in UNITS_VARIO.items():
+        obj = os.path.join(OBJ, name + ".o")
+        if force or _stale(obj, vario_deps(name), FLAGS):
+            todo_vario.append((name, FLAGS, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
 
     def run(job):
         name, flags, cmd = job
@@ -137,13 +157,19 @@ def _build_locked(force, verbose, jobs):
 
     todo.sort(key=lambda j: -COST.get(j[0].rstrip("0123456789"), 0))
     with ThreadPoolExecutor(max_workers=jobs or min(len(UNITS), os.cpu_count() or 4)) as ex:
-        list(ex.map(run, todo))
-    link = [cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + [os.path.join(OBJ, n + ".o") for n in UNITS] + ["-o", OUT + pid, "-ldl", "-Wl,-s"]
+        list(ex.map(run, todo + todo_vario))
     # (-s: no static symbol table -- 90 kB; the C ABI and the kernels' host stubs are dynamic symbols, `nm -D` lists them)
-    if verbose:
-        print(" ".join(link), flush=True)
-    subprocess.run(link, check=True)
-    os.replace(OUT + pid, OUT)
+    links = []
+    if relink or _stale(OUT, all_sources()):
+        links.append((OUT, [os.path.join(OBJ, n + ".o") for n in UNITS], ["-ldl", "-Wl,-s"]))
+    if todo_vario or _stale(OUT_VARIO, [d for n in UNITS_VARIO for d in vario_deps(n)]):
+        links.append((OUT_VARIO, [os.path.join(OBJ, n + ".o") for n in UNITS_VARIO], ["-Wl,-s"]))
+    for out, objs, tail in links:
+        link = [cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out + pid] + tail
+        if verbose:
+            print(" ".join(link), flush=True)
+        subprocess.run(link, check=True)
+        os.replace(out + pid, out)
     return OUT
 
 

@@ -809,6 +809,39 @@ class _KrigingBase:
         if h is not None and h.n_devices > 1:
             raise ValueError("%s: this object's handle spans a device group of %d devices; %s" % (name, h.n_devices, one_device))
 
+    # ---------------------------------------------------------------- anisotropy tools (libmikvario.so, variography.py)
+    def _variography_stations(self, name):
+        """The raw station coordinates and values of a 2-D euclidean object -- before the anisotropy adjustment, which is what the tool is
+        there to find.  Every refusal is raised before libmikvario.so is loaded."""
+        if self._ndim == 3:
+            raise ValueError("%s: directions in 3-D need an azimuth and a dip; only the 2-D classes have this tool" % name)
+        if getattr(self, "coordinates_type", "euclidean") == "geographic":
+            raise ValueError("%s: coordinates_type='geographic' is not built; directions and lag vectors are planar" % name)
+        self._refuse_group(self._handle, name, "the pairs are binned on one device")
+        return self.X_ORIG, self.Y_ORIG, self._values()
+
+    def directional_variogram(self, azimuths, tolerance=22.5, nlags=6, maxlag=None, edges=None, bandwidth=None):
+        """Directional experimental semivariograms of this object's stations and values, in the caller's coordinates -- BEFORE the anisotropy
+        adjustment: ``lags, semivariance, counts = obj.directional_variogram(azimuths, tolerance=22.5, nlags=6, maxlag=None, edges=None,
+        bandwidth=None)``, each (A, nlags).  azimuths in degrees counter-clockwise from +x, the convention of ``anisotropy_angle``.  The
+        arguments and results are ``pykrige_amd.variography.directional_variogram``'s.  The 3-D classes, coordinates_type='geographic' and
+        a handle that spans a device group raise ``ValueError``."""
+        from . import variography
+
+        x, y, v = self._variography_stations("directional_variogram")
+        return variography.directional_variogram(x, y, v, azimuths, tolerance=tolerance, nlags=nlags, maxlag=maxlag, edges=edges,
+                                                 bandwidth=bandwidth)
+
+    def variogram_map(self, nx, ny, dx, dy):
+        """Variogram map of this object's stations and values, in the caller's coordinates -- BEFORE the anisotropy adjustment:
+        ``semivariance, counts = obj.variogram_map(nx, ny, dx, dy)``, each (2 ny + 1, 2 nx + 1), cells of dx x dy centred on lag zero.
+        The arguments and results are ``pykrige_amd.variography.variogram_map``'s.  The 3-D classes, coordinates_type='geographic' and a
+        handle that spans a device group raise ``ValueError``."""
+        from . import variography
+
+        x, y, v = self._variography_stations("variogram_map")
+        return variography.variogram_map(x, y, v, nx, ny, dx, dy)
+
     def _resident_problem(self, P, name, one_device):
         """The handle with this object's problem set (only if its key changed) and the points P loaded: (handle, factor key).
         _upload_and_factor without its factor(): mik_predict_cov / mik_predict_block refuse (an oversized P among the reasons) before
