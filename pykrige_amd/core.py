@@ -55,6 +55,18 @@ def anisotropy_matrices(ndim, scaling, angle):
     return np.dot(rot_z, np.dot(rot_y, rot_x)), np.array([1.0, scaling[0], scaling[1]], dtype=np.float64)
 
 
+def anisotropy_axes(angle):
+    """The three rows of the 3-D rotation that ``anisotropy_matrices(3, ...)`` builds from ``angle = (anisotropy_angle_x, _y, _z)`` in
+    degrees: (3, 3), row k the raw-space unit direction of the adjusted k-th axis (the adjusted coordinates are stretch . rot . raw, so
+    the adjusted x of a raw vector h is rows[0] . h).  The same NumPy calls: the rows are bit-identical to what the constructor multiplies
+    by.  ``variography3d.directional_variogram_3d(..., directions=anisotropy_axes(angles))`` is the check of a candidate anisotropy: along
+    these directions the ranges should stand as 1 : 1 / scaling_y : 1 / scaling_z."""
+    ang = np.asarray(angle, dtype=np.float64).ravel()
+    if ang.size != 3 or not np.all(np.isfinite(ang)):
+        raise ValueError("anisotropy_axes: angle must be three finite angles in degrees (anisotropy_angle_x, _y, _z)")
+    return np.array(anisotropy_matrices(3, [1.0, 1.0], ang)[0])
+
+
 BLOCK_MAX_NODES = 512  # mik_predict_block: the node offsets of a block live in LDS
 
 

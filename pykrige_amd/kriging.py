@@ -814,7 +814,8 @@ class _KrigingBase:
         """The raw station coordinates and values of a 2-D euclidean object -- before the anisotropy adjustment, which is what the tool is
         there to find.  Every refusal is raised before libmikvario.so is loaded."""
         if self._ndim == 3:
-            raise ValueError("%s: directions in 3-D need an azimuth and a dip; only the 2-D classes have this tool" % name)
+            raise ValueError("%s: directions in 3-D need an azimuth and a dip; only the 2-D classes have this tool (the 3-D classes have "
+                             "%s_3d)" % (name, name))
         if getattr(self, "coordinates_type", "euclidean") == "geographic":
             raise ValueError("%s: coordinates_type='geographic' is not built; directions and lag vectors are planar" % name)
         self._refuse_group(self._handle, name, "the pairs are binned on one device")
@@ -841,6 +842,40 @@ class _KrigingBase:
 
         x, y, v = self._variography_stations("variogram_map")
         return variography.variogram_map(x, y, v, nx, ny, dx, dy)
+
+    # ---------------------------------------------------------------- the same tools for the 3-D classes (libmikvario3.so, variography3d.py)
+    def _variography3d_stations(self, name):
+        """The raw station coordinates and values of a 3-D object -- before the anisotropy adjustment.  Every refusal is raised before
+        libmikvario3.so is loaded."""
+        if self._ndim != 3:
+            raise ValueError("%s: this is a 2-D object; the 2-D classes have %s (azimuths only)" % (name, name[:-3]))
+        self._refuse_group(self._handle, name, "the pairs are binned on one device")
+        return self.X_ORIG, self.Y_ORIG, self.Z_ORIG, self._values()
+
+    def directional_variogram_3d(self, azimuths=None, dips=None, directions=None, tolerance=22.5, nlags=6, maxlag=None, edges=None,
+                                 bandwidth=None):
+        """Directional experimental semivariograms of this 3-D object's stations and values, in the caller's coordinates -- BEFORE the
+        anisotropy adjustment: ``lags, semivariance, counts = obj.directional_variogram_3d(azimuths=None, dips=None, directions=None,
+        tolerance=22.5, nlags=6, maxlag=None, edges=None, bandwidth=None)``, each (A, nlags).  Give azimuths and dips in degrees (azimuth
+        counter-clockwise from +x, dip upward toward +z) or directions, (A, 3) vectors; ``directions=core.anisotropy_axes([angle_x, angle_y,
+        angle_z])`` looks along the principal axes of a candidate rotation.  The arguments and results are
+        ``pykrige_amd.variography3d.directional_variogram_3d``'s.  A 2-D object (use ``directional_variogram``) and a handle that spans a
+        device group raise ``ValueError``."""
+        from . import variography3d
+
+        x, y, z, v = self._variography3d_stations("directional_variogram_3d")
+        return variography3d.directional_variogram_3d(x, y, z, v, azimuths=azimuths, dips=dips, directions=directions, tolerance=tolerance,
+                                                      nlags=nlags, maxlag=maxlag, edges=edges, bandwidth=bandwidth)
+
+    def variogram_map_3d(self, nx, ny, nz, dx, dy, dz):
+        """3-D variogram map of this 3-D object's stations and values, in the caller's coordinates -- BEFORE the anisotropy adjustment:
+        ``semivariance, counts = obj.variogram_map_3d(nx, ny, nz, dx, dy, dz)``, each (2 nz + 1, 2 ny + 1, 2 nx + 1), cells of dx x dy x dz
+        centred on lag zero.  The arguments and results are ``pykrige_amd.variography3d.variogram_map_3d``'s.  A 2-D object (use
+        ``variogram_map``) and a handle that spans a device group raise ``ValueError``."""
+        from . import variography3d
+
+        x, y, z, v = self._variography3d_stations("variogram_map_3d")
+        return variography3d.variogram_map_3d(x, y, z, v, nx, ny, nz, dx, dy, dz)
 
     def _resident_problem(self, P, name, one_device):
         """The handle with this object's problem set (only if its key changed) and the points P loaded: (handle, factor key).
