@@ -1,4 +1,4 @@
-"""Builds pykrige_amd/libmikrige.so, pykrige_amd/libmikvario.so and pykrige_amd/libmikvario3.so (HIP, gfx950) in-tree.  `python -m pykrige_amd.build [--force] [-j N]`.
+"""Builds pykrige_amd/libmikrige.so, pykrige_amd/libmikvario.so, pykrige_amd/libmikvario3.so and pykrige_amd/libmiklik.so (HIP, gfx950) in-tree.  `python -m pykrige_amd.build [--force] [-j N]`.
 
 The library is ten translation units compiled in parallel (objects under pykrige_amd/csrc/build/, git- and gpurun-ignored) and
 linked into one shared object; only the units whose sources or flags changed are recompiled (the command line of every object is
@@ -19,6 +19,10 @@ a frozen kernel list (tests/test_abi_and_host.py): new device features go here. 
 libmikvario3.so (include/mikvario3.h: the same tools for the 3-D classes -- directions by unit vector, maps of lag-vector cells in x, y, z)
 is a third library of one unit, mik_vario3.hip, built the same way.  The second library's exports and kernels are pinned by
 tests/test_directional_variogram_host.py, so the 3-D kernels have a shared object of their own; nothing is linked between the three.
+
+libmiklik.so (include/miklik.h: log det C and W^T C^-1 W of a station set under a variogram model, for the ML / REML fit of likelihood.py)
+is a fourth library of one unit, mik_lik.hip, built the same way: the second and third libraries are pinned by their host tests as the
+first is, and the call needs no handle and no inverse.  Nothing is linked between the four.
 """
 import os
 import shutil
@@ -36,6 +40,8 @@ API = os.path.join(ROOT, "include", "mikrige.h")
 API_VARIO = os.path.join(ROOT, "include", "mikvario.h")
 OUT_VARIO3 = os.path.join(HERE, "libmikvario3.so")
 API_VARIO3 = os.path.join(ROOT, "include", "mikvario3.h")
+OUT_LIK = os.path.join(HERE, "libmiklik.so")
+API_LIK = os.path.join(ROOT, "include", "miklik.h")
 COMMON = ["mik_host.h", "mik_dev.h"]
 # object name -> (source, extra headers it includes, extra flags)
 UNITS = {
@@ -54,6 +60,8 @@ UNITS = {
 UNITS_VARIO = {"mik_vario": ("mik_vario.hip", ["mik_k_vario.h"])}
 # the third library, in the same form
 UNITS_VARIO3 = {"mik_vario3": ("mik_vario3.hip", ["mik_k_vario3.h"])}
+# the fourth library, in the same form
+UNITS_LIK = {"mik_lik": ("mik_lik.hip", ["mik_k_lik.h"])}
 # --offload-compress: the code objects travel zstd-compressed inside the fat binary (16.9 -> 2.3 MB of .so; the HIP runtime unpacks them at load);
 # level 19 instead of the default 3 takes another 3 % off and no measurable compile time (the time is in code generation)
 COMPRESS = ["--offload-compress", "--offload-compression-level=19"]
@@ -107,14 +115,20 @@ def vario3_deps(name):
     return [os.path.join(CSRC, f) for f in [src] + hdrs] + [API_VARIO3]
 
 
+def lik_deps(name):
+    src, hdrs = UNITS_LIK[name]
+    return [os.path.join(CSRC, f) for f in [src] + hdrs] + [API_LIK]
+
+
 def up_to_date():
     return (not _stale(OUT, all_sources()) and not _stale(OUT_VARIO, [d for n in UNITS_VARIO for d in vario_deps(n)])
-            and not _stale(OUT_VARIO3, [d for n in UNITS_VARIO3 for d in vario3_deps(n)]))
+            and not _stale(OUT_VARIO3, [d for n in UNITS_VARIO3 for d in vario3_deps(n)])
+            and not _stale(OUT_LIK, [d for n in UNITS_LIK for d in lik_deps(n)]))
 
 
 def build_library(force=False, verbose=False, jobs=None):
-    """Compile the three C-ABI libraries for gfx950; returns the path of libmikrige.so (OUT; libmikvario.so is OUT_VARIO, libmikvario3.so
-    OUT_VARIO3).
+    """Compile the four C-ABI libraries for gfx950; returns the path of libmikrige.so (OUT; libmikvario.so is OUT_VARIO, libmikvario3.so
+    OUT_VARIO3, libmiklik.so OUT_LIK).
     Cross-compiles without a GPU."""
     if not force and up_to_date():
         return OUT
@@ -148,6 +162,11 @@ def _build_locked(force, verbose, jobs):
         obj = os.path.join(OBJ, name + ".o")
         if force or _stale(obj, vario3_deps(name), FLAGS):
             todo_vario3.append((name, FLAGS, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
+    todo_lik = []
+    for name, (src, _) in UNITS_LIK.items():
+        obj = os.path.join(OBJ, name + ".o")
+        if force or _stale(obj, lik_deps(name), FLAGS):
+            todo_lik.append((name, FLAGS, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
 
     def run(job):
         name, flags, cmd = job
@@ -177,7 +196,7 @@ def _build_locked(force, verbose, jobs):
 
     todo.sort(key=lambda j: -COST.get(j[0].rstrip("0123456789"), 0))
     with ThreadPoolExecutor(max_workers=jobs or min(len(UNITS), os.cpu_count() or 4)) as ex:
-        list(ex.map(run, todo + todo_vario + todo_vario3))
+        list(ex.map(run, todo + todo_vario + todo_vario3 + todo_lik))
     # (-s: no static symbol table -- 90 kB; the C ABI and the kernels' host stubs are dynamic symbols, `nm -D` lists them)
     links = []
     if relink or _stale(OUT, all_sources()):
@@ -186,6 +205,8 @@ def _build_locked(force, verbose, jobs):
         links.append((OUT_VARIO, [os.path.join(OBJ, n + ".o") for n in UNITS_VARIO], ["-Wl,-s"]))
     if todo_vario3 or _stale(OUT_VARIO3, [d for n in UNITS_VARIO3 for d in vario3_deps(n)]):
         links.append((OUT_VARIO3, [os.path.join(OBJ, n + ".o") for n in UNITS_VARIO3], ["-Wl,-s"]))
+    if todo_lik or _stale(OUT_LIK, [d for n in UNITS_LIK for d in lik_deps(n)]):
+        links.append((OUT_LIK, [os.path.join(OBJ, n + ".o") for n in UNITS_LIK], ["-Wl,-s"]))
     for out, objs, tail in links:
         link = [cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out + pid] + tail
         if verbose:

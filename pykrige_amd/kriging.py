@@ -877,6 +877,70 @@ class _KrigingBase:
         x, y, z, v = self._variography3d_stations("variogram_map_3d")
         return variography3d.variogram_map_3d(x, y, z, v, nx, ny, nz, dx, dy, dz)
 
+    # ---------------------------------------------------------------- the likelihood of the variogram (libmiklik.so, likelihood.py)
+    def _likelihood_problem(self, name, anisotropy):
+        """(coordinate columns, values, drift, anisotropy keywords) of this object for likelihood.py.  Every refusal is raised before
+        libmiklik.so is loaded."""
+        from . import likelihood
+
+        if getattr(self, "coordinates_type", "euclidean") == "geographic":
+            raise ValueError("%s: coordinates_type='geographic' is not built; the covariance is a function of the Euclidean distance" % name)
+        self._refuse_group(self._handle, name, "the covariance matrix is factored on one device")
+        likelihood._check_model(name, self.variogram_model)
+        drift = None
+        if self._universal:
+            others = [t for t in ("external_Z_drift", "point_log_drift", "specified_drift", "functional_drift") if getattr(self, t, False)]
+            if others:
+                raise NotImplementedError("%s: regional_linear is the only drift term whose trend is built (X = [1, x, y(, z)] of the "
+                                          "adjusted coordinates); this object also has %s" % (name, ", ".join(t[:-6] for t in others)))
+            if self._regional_linear():
+                drift = "regional_linear"
+        own = likelihood._ANIS2 if self._ndim == 2 else likelihood._ANIS3
+        unknown = set(anisotropy) - set(own)
+        if unknown:
+            raise TypeError("%s: unexpected argument %s (the anisotropy overrides of this class are %s)"
+                            % (name, ", ".join(sorted(unknown)), ", ".join(own)))
+        anis = {k: getattr(self, k) for k in own}
+        anis.update({k: v for k, v in anisotropy.items() if v is not None})
+        cols = [self.X_ORIG, self.Y_ORIG] + ([self.Z_ORIG] if self._ndim == 3 else [])
+        return cols, self._values(), drift, anis
+
+    def _list_parameters(self):
+        psill, rng, nugget = (float(v) for v in self.variogram_model_parameters)
+        return [psill + nugget, rng, nugget]
+
+    def neg_log_likelihood(self, variogram_parameters=None, reml=True, **anisotropy):
+        """The negative Gaussian log-likelihood of this object's stations and values under its variogram model, one Cholesky factorisation
+        on the GPU: ``nll = obj.neg_log_likelihood(variogram_parameters=None, reml=True, **anisotropy)``.  variogram_parameters=None takes
+        the object's current parameters, otherwise the constructor's forms (a list with the FULL sill, or a dict).  The anisotropy is the
+        object's unless overridden by the constructor's keywords (``anisotropy_scaling``, ``anisotropy_angle``; 3-D:
+        ``anisotropy_scaling_y``, ``anisotropy_scaling_z``, ``anisotropy_angle_x``, ``anisotropy_angle_y``, ``anisotropy_angle_z``).  The
+        mean is constant; on the universal classes with ``regional_linear`` the trend is X = [1, x, y(, z)] of the adjusted coordinates,
+        and any other drift term raises ``NotImplementedError``.  reml=True is the restricted likelihood, False the full one; the formulas
+        are ``pykrige_amd.likelihood.neg_log_likelihood``'s.  A matrix that is not positive definite gives ``inf``.  'linear', 'power'
+        (ValueError) and 'custom' (NotImplementedError) models, coordinates_type='geographic' and a handle that spans a device group
+        (ValueError) are refused before anything is loaded."""
+        from . import likelihood
+
+        cols, v, drift, anis = self._likelihood_problem("neg_log_likelihood", anisotropy)
+        par = self._list_parameters() if variogram_parameters is None else variogram_parameters
+        return likelihood.neg_log_likelihood(*cols, v, self.variogram_model, par, drift=drift, reml=reml, **anis)
+
+    def fit_variogram_ml(self, start=None, fit_anisotropy=False, reml=True, bounds=None, **anisotropy):
+        """Maximum-likelihood / REML fit of this object's variogram model (and, with fit_anisotropy, of its anisotropy) to its stations
+        and values -- binning-free: ``fit = obj.fit_variogram_ml(start=None, fit_anisotropy=False, reml=True, bounds=None, **anisotropy)``.
+        start=None begins at the object's current parameters and anisotropy (the constructor's least-squares fit, unless parameters were
+        given).  Returns ``pykrige_amd.likelihood.MLFit``: ``fit.variogram_parameters`` in the constructor's list form and
+        ``fit.anisotropy`` as the constructor's keywords, ``fit.nll``, ``fit.n_evaluations``, ``fit.success``; the object itself is not
+        changed -- hand the fit to ``update_variogram_model`` or to a new object.  The trend and the refusals are those of
+        ``neg_log_likelihood``: 'linear', 'power' and 'custom' models, coordinates_type='geographic', a device group, and on the universal
+        classes any drift term but ``regional_linear`` (``NotImplementedError``)."""
+        from . import likelihood
+
+        cols, v, drift, anis = self._likelihood_problem("fit_variogram_ml", anisotropy)
+        return likelihood.fit_variogram_ml(*cols, v, self.variogram_model, start=self._list_parameters() if start is None else start,
+                                           fit_anisotropy=fit_anisotropy, drift=drift, reml=reml, bounds=bounds, **anis)
+
     def _resident_problem(self, P, name, one_device):
         """The handle with this object's problem set (only if its key changed) and the points P loaded: (handle, factor key).
         _upload_and_factor without its factor(): mik_predict_cov / mik_predict_block refuse (an oversized P among the reasons) before

@@ -1,0 +1,472 @@
+"""The Gaussian likelihood of a variogram model on the GPU: maximum likelihood and restricted maximum likelihood (REML) fits of psill,
+range, nugget and the anisotropy, binning-free.
+
+ctypes binding of libmiklik.so (include/miklik.h), a fourth library beside libmikrige.so, libmikvario.so and libmikvario3.so, loaded on
+first use.  NumPy + ctypes (+ scipy.optimize for the fit).  There is no CPU fallback: a missing library or no visible GPU raises.  Every
+argument error is a ValueError (NotImplementedError for a custom model) raised here, before the library is loaded.
+
+One evaluation is one device call: the N x N covariance matrix C of the stations is assembled, Cholesky-factored and thrown away;
+``logdet = log det C`` and ``G = W^T C^-1 W`` for a handful of columns W come back.  With W = [V | X] (fields and trend columns) the small
+algebra of the likelihood is NumPy's.
+"""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+
+from . import core
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libmiklik.so")
+
+MLK_OK, MLK_EINVAL, MLK_ENOTPD, MLK_EHIP = 0, -1, -2, -3
+ABI_VERSION = 1  # include/miklik.h MLK_ABI_VERSION
+MAXCOLS, MAXFIELDS, MAXTREND = 40, 32, 8  # MLK_MAXCOLS = MAXFIELDS + MAXTREND
+MODEL_IDS = {"gaussian": 0, "exponential": 1, "spherical": 2, "hole-effect": 3}  # MLK_GAUSSIAN ...
+
+_dp = C.POINTER(C.c_double)
+_i32p = C.POINTER(C.c_int32)
+
+# every entry point include/miklik.h declares: name -> (restype, argtypes)
+SIGNATURES = {
+    "mlk_abi_version": (C.c_int, []),
+    "mlk_last_error": (C.c_char_p, []),
+    "mlk_gram": (C.c_int, [C.c_int, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_double, C.c_double, C.c_double, _dp, C.c_int32, _dp, _dp,
+                           _i32p]),
+}
+
+_lib = None
+
+
+def load():
+    """dlopen libmiklik.so and declare the signatures.  Raises ImportError if it has not been built or is stale."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise ImportError(
+            "pykrige_amd: %s is missing -- build it with `python -m pykrige_amd.build` "
+            "(needs hipcc; there is no CPU fallback)" % LIB_PATH)
+    lib = C.CDLL(LIB_PATH)
+    have = getattr(lib, "mlk_abi_version", None)
+    version = None
+    if have is not None:
+        have.restype, have.argtypes = SIGNATURES["mlk_abi_version"]
+        version = have()
+    stale = "pykrige_amd: %s %%s, this package was written against ABI version %d -- rebuild it (`python -m pykrige_amd.build --force`)" % (
+        LIB_PATH, ABI_VERSION)
+    if version != ABI_VERSION:
+        raise ImportError(stale % ("has no mlk_abi_version" if version is None else "has ABI version %d" % version))
+    for name, (res, args) in SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise ImportError(stale % ("does not export %s" % name)) from None
+        fn.restype = res
+        fn.argtypes = args
+    _lib = lib
+    return lib
+
+
+def _device():
+    return int(os.environ.get("MIK_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+
+
+def _check_model(who, model):
+    if model == "custom" or callable(model) or hasattr(model, "pykrige_kwargs"):
+        raise NotImplementedError("%s: variogram_model='custom' is evaluated on the host; the likelihood needs a covariance the device can "
+                                  "evaluate" % who)
+    if model in ("linear", "power"):
+        raise ValueError("%s: the '%s' variogram is unbounded -- no covariance exists; use one of %s"
+                         % (who, model, ", ".join(repr(k) for k in MODEL_IDS)))
+    if model not in MODEL_IDS:
+        raise ValueError("%s: variogram_model must be one of %s, got %r" % (who, ", ".join(repr(k) for k in MODEL_IDS), model))
+
+
+def gram(coords, model, parameters, W):
+    """``logdet, G = gram(coords, model, parameters, W)``: log det C and W^T C^-1 W on the GPU, one call of ``mlk_gram``.
+
+    coords: (N, 2) or (N, 3) anisotropy-adjusted Euclidean station coordinates, N >= 2.  model: 'gaussian', 'exponential', 'spherical' or
+    'hole-effect'.  parameters: the internal list [psill, range, nugget] (partial sill), psill > 0, range > 0, nugget >= 0.  W: (N,) or
+    (N, m) columns, 1 <= m <= 40.
+
+    C_ii = psill + nugget and, for i != j, C_ij = (psill + nugget) - gamma(d_ij) with the model formula of ``core.variogram_value`` in
+    float64 -- also at d = 0: two coincident distinct stations have C_ij = psill.  G is (m, m) and exactly symmetric.  Both results are
+    reproducible bit for bit from run to run, and an entry of G does not depend on where its two columns stand in W.  If C is not
+    positive definite in float64, logdet is ``inf`` and G is filled with NaN.  Argument errors raise ValueError before the library is
+    loaded; there is no CPU fallback."""
+    who = "gram"
+    _check_model(who, model)
+    X = np.asarray(coords, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] not in (2, 3):
+        raise ValueError("%s: coords must have shape (N, 2) or (N, 3), got %s" % (who, np.shape(coords)))
+    n, ndim = X.shape
+    if n < 2:
+        raise ValueError("%s: need at least two stations" % who)
+    try:
+        psill, rng, nugget = (float(v) for v in parameters)
+    except (TypeError, ValueError):
+        raise ValueError("%s: parameters must be the three numbers [psill, range, nugget]" % who) from None
+    if not (math.isfinite(psill) and math.isfinite(rng) and math.isfinite(nugget) and psill > 0.0 and rng > 0.0 and nugget >= 0.0):
+        raise ValueError("%s: need finite psill > 0, range > 0 and nugget >= 0, got %r" % (who, [psill, rng, nugget]))
+    Wa = np.asarray(W, dtype=np.float64)
+    if Wa.ndim == 1:
+        Wa = Wa[:, None]
+    if Wa.ndim != 2 or Wa.shape[0] != n or not 1 <= Wa.shape[1] <= MAXCOLS:
+        raise ValueError("%s: W must have shape (N,) or (N, m) with N = %d stations and 1 <= m <= %d columns (MLK_MAXCOLS), got %s"
+                         % (who, n, MAXCOLS, np.shape(W)))
+    if not np.all(np.isfinite(X)):
+        raise ValueError("%s: station coordinates must be finite" % who)
+    if not np.all(np.isfinite(Wa)):
+        raise ValueError("%s: W must be finite" % who)
+    m = int(Wa.shape[1])
+    ct = np.ascontiguousarray(X.T)
+    wt = np.ascontiguousarray(Wa.T)
+    G = np.zeros((m, m))
+    logdet = C.c_double(0.0)
+    info = C.c_int32(0)
+    lib = load()
+    rc = lib.mlk_gram(_device(), n, ndim, ct.ctypes.data_as(_dp), MODEL_IDS[model], psill, rng, nugget, wt.ctypes.data_as(_dp), m,
+                      C.byref(logdet), G.ctypes.data_as(_dp), C.byref(info))
+    if rc == MLK_ENOTPD:
+        return math.inf, np.full((m, m), np.nan)
+    if rc != MLK_OK:
+        msg = (lib.mlk_last_error() or b"").decode("utf-8", "replace")
+        if rc == MLK_EINVAL:
+            raise ValueError(msg)
+        raise RuntimeError("libmiklik: %s (code %d)" % (msg, rc))
+    return float(logdet.value), G
+
+
+# ------------------------------------------------------------------------------------------------------------- the likelihood
+_ANIS2 = ("anisotropy_scaling", "anisotropy_angle")
+_ANIS3 = ("anisotropy_scaling_y", "anisotropy_scaling_z", "anisotropy_angle_x", "anisotropy_angle_y", "anisotropy_angle_z")
+
+
+def _split(who, args, kw, names):
+    """(x, y[, z], values, *rest) -> raw (N, d) coordinates, the values and the remaining named arguments: the first string among the
+    positional arguments is the variogram model, which tells 2-D from 3-D."""
+    args = list(args)
+    at = next((k for k, a in enumerate(args) if isinstance(a, str) or hasattr(a, "pykrige_kwargs")), len(args))
+    if at < len(args):
+        for name, a in zip(names, args[at:]):
+            if name in kw:
+                raise TypeError("%s: %s given twice" % (who, name))
+            kw[name] = a
+        if len(args) - at > len(names):
+            raise TypeError("%s: too many positional arguments" % who)
+        args = args[:at]
+    if len(args) not in (3, 4):
+        raise TypeError("%s: the leading arguments are x, y, values or x, y, z, values" % who)
+    cols = [np.atleast_1d(np.squeeze(np.asarray(a, dtype=np.float64))) for a in args[:-1]]
+    if any(c.ndim != 1 or c.shape != cols[0].shape for c in cols):
+        raise ValueError("%s: x, y%s must be one-dimensional arrays of the same length" % (who, " and z" if len(cols) == 3 else ""))
+    return np.vstack(cols).T, args[-1], kw
+
+
+def _fields(who, values, n):
+    v = np.asarray(values, dtype=np.float64)
+    many = v.ndim == 2
+    if v.ndim == 1:
+        v = v[:, None]
+    if v.ndim != 2 or v.shape[0] != n or not 1 <= v.shape[1] <= MAXFIELDS:
+        raise ValueError("%s: values must have shape (N,) or (N, F) with N = %d stations and 1 <= F <= %d fields, got %s"
+                         % (who, n, MAXFIELDS, np.shape(values)))
+    if not np.all(np.isfinite(v)):
+        raise ValueError("%s: values must be finite" % who)
+    return v, many
+
+
+def _anisotropy(who, ndim, kw):
+    """The constructor's anisotropy arguments of this dimension -> (scaling list, angle list)."""
+    own, other = (_ANIS2, _ANIS3) if ndim == 2 else (_ANIS3, _ANIS2)
+    for name in other:
+        if kw.get(name) is not None:
+            raise ValueError("%s: %s is an argument of the %s classes; these are %d-D stations" % (who, name, "3-D" if ndim == 2 else "2-D",
+                                                                                                   ndim))
+    vals = [float(kw[name]) if kw.get(name) is not None else (1.0 if "scaling" in name else 0.0) for name in own]
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError("%s: the anisotropy arguments must be finite" % who)
+    nscale = 1 if ndim == 2 else 2
+    if not all(v > 0.0 for v in vals[:nscale]):
+        raise ValueError("%s: an anisotropy scaling must be positive" % who)
+    return vals[:nscale], vals[nscale:]
+
+
+def _adjust(raw, scaling, angle):
+    """core.adjust_for_anisotropy about the constructor's centre: the middle of the bounding box."""
+    center = [(float(np.amax(c)) + float(np.amin(c))) / 2.0 for c in raw.T]
+    return core.adjust_for_anisotropy(raw, center, scaling, angle)
+
+
+def _trend(who, drift, n, adjusted):
+    """X = [1 | drift]: (N, p), p = 1 + q <= 8, of full column rank.  drift='regional_linear': the adjusted coordinates, the trend of
+    the universal classes' regional_linear term."""
+    X = np.ones((n, 1))
+    if isinstance(drift, str):
+        if drift != "regional_linear":
+            raise ValueError("%s: drift must be None, an (N, q) array or 'regional_linear', got %r" % (who, drift))
+        X = np.hstack([X, adjusted])
+    elif drift is not None:
+        d = np.asarray(drift, dtype=np.float64)
+        if d.ndim == 1:
+            d = d[:, None]
+        if d.ndim != 2 or d.shape[0] != n:
+            raise ValueError("%s: drift must have shape (N, q) with N = %d stations, got %s" % (who, n, np.shape(drift)))
+        if not np.all(np.isfinite(d)):
+            raise ValueError("%s: drift must be finite" % who)
+        X = np.hstack([X, d])
+    p = X.shape[1]
+    if p > MAXTREND:
+        raise ValueError("%s: at most %d trend columns, the ones column included (p = 1 + q <= %d), got %d" % (who, MAXTREND, MAXTREND, p))
+    if p > n or np.linalg.matrix_rank(X) < p:
+        raise ValueError("%s: the trend matrix X = [1 | drift] is rank-deficient" % who)
+    return X
+
+
+def _pieces(X):
+    """log det(X^T X), from the Cholesky factor of the p x p matrix."""
+    return 2.0 * float(np.sum(np.log(np.diag(np.linalg.cholesky(X.T @ X)))))
+
+
+def nll_from_gram(n, logdet, G, nfields, reml, logdet_xtx):
+    """The negative log-likelihoods of nfields fields from ``logdet`` and ``G = W^T C^-1 W`` of W = [V | X]: with
+    beta_f = G_xx^-1 G_xv[:, f] and Q_f = G_vv[f, f] - G_xv[:, f]^T beta_f,
+    ML: 1/2 [N log 2 pi + logdet + Q_f];  REML: 1/2 [(N - p) log 2 pi - log det(X^T X) + logdet + log det G_xx + Q_f].
+    Each field is worked on its own, so that a field's number does not depend on the fields beside it.  (F,) float64; inf where C or
+    G_xx is not positive definite."""
+    F = int(nfields)
+    out = np.full(F, np.inf)
+    if not math.isfinite(logdet) or not np.all(np.isfinite(G)):
+        return out
+    Gxx = G[F:, F:]
+    p = Gxx.shape[0]
+    try:
+        Lx = np.linalg.cholesky(Gxx)
+    except np.linalg.LinAlgError:
+        return out
+    logdet_gxx = 2.0 * float(np.sum(np.log(np.diag(Lx))))
+    for f in range(F):
+        g = np.ascontiguousarray(G[F:, f])
+        y = np.zeros(p)  # forward substitution Lx y = g, one field at a time
+        for i in range(p):
+            y[i] = (g[i] - float(np.dot(Lx[i, :i], y[:i]))) / Lx[i, i]
+        q = float(G[f, f]) - float(np.dot(y, y))
+        if reml:
+            out[f] = 0.5 * ((n - p) * math.log(2.0 * math.pi) - logdet_xtx + logdet + logdet_gxx + q)
+        else:
+            out[f] = 0.5 * (n * math.log(2.0 * math.pi) + logdet + q)
+    return out
+
+
+def _internal_parameters(who, model, variogram_parameters):
+    if variogram_parameters is None:
+        raise ValueError("%s: variogram_parameters must be given (a list [sill, range, nugget] or a dict)" % who)
+    plist = core.make_variogram_parameter_list(model, variogram_parameters if type(variogram_parameters) in (list, dict)
+                                               else list(variogram_parameters))
+    psill, rng, nugget = (float(v) for v in plist)
+    if not (math.isfinite(psill) and math.isfinite(rng) and math.isfinite(nugget) and psill > 0.0 and rng > 0.0 and nugget >= 0.0):
+        raise ValueError("%s: need a finite partial sill > 0 (sill - nugget), range > 0 and nugget >= 0, got psill = %r, range = %r, "
+                         "nugget = %r" % (who, psill, rng, nugget))
+    return [psill, rng, nugget]
+
+
+_NLL_NAMES = ("variogram_model", "variogram_parameters")
+
+
+def neg_log_likelihood(x, y, *args, **kwargs):
+    """The negative Gaussian log-likelihood of the stations under a variogram model, one Cholesky factorisation on the GPU.
+
+    ``neg_log_likelihood(x, y[, z], values, variogram_model, variogram_parameters, anisotropy_scaling=1.0, anisotropy_angle=0.0,
+    drift=None, reml=True)`` -- for 3-D stations the anisotropy arguments are ``anisotropy_scaling_y, anisotropy_scaling_z,
+    anisotropy_angle_x, anisotropy_angle_y, anisotropy_angle_z``, as in the constructors.
+
+    Returns a float for (N,) values, or (F,) for (N, F) values with F <= 32: all F fields ride as columns of W through the one
+    factorisation, and field f's number is bit for bit that of the one-field call.  variogram_parameters takes the forms of the
+    constructors: a list [sill, range, nugget] with the FULL sill, or a dict.  The coordinates are adjusted on the host by
+    ``core.adjust_for_anisotropy`` about the constructor's centre (the middle of the bounding box).  drift is None -- a constant mean,
+    X = 1 -- or an (N, q) array whose columns follow the ones column, p = 1 + q <= 8, or 'regional_linear': the adjusted coordinates
+    (the regional_linear term of the universal classes).
+
+    With W = [V | X], G = W^T C^-1 W, beta_f = G_xx^-1 G_xv[:, f] and Q_f = G_vv[f, f] - G_xv[:, f]^T beta_f (the generalised
+    least-squares residual sum of squares):
+    ML (reml=False): 1/2 [N log 2 pi + log det C + Q_f];
+    REML (reml=True): 1/2 [(N - p) log 2 pi - log det(X^T X) + log det C + log det G_xx + Q_f].
+    A covariance matrix that is not positive definite in float64 gives ``inf``.  'linear' and 'power' (unbounded: no covariance exists)
+    and non-finite input raise ValueError, a rank-deficient X raises ValueError, 'custom' raises NotImplementedError -- all before the
+    library is loaded.  There is no CPU fallback."""
+    who = "neg_log_likelihood"
+    raw, values, kw = _split(who, (x, y) + args, dict(kwargs), _NLL_NAMES)
+    unknown = set(kw) - set(_NLL_NAMES) - set(_ANIS2) - set(_ANIS3) - {"drift", "reml"}
+    if unknown:
+        raise TypeError("%s: unexpected argument %s" % (who, ", ".join(sorted(unknown))))
+    if "variogram_model" not in kw:
+        raise TypeError("%s: variogram_model is required" % who)
+    model = kw["variogram_model"]
+    _check_model(who, model)
+    n, ndim = raw.shape
+    if n < 2:
+        raise ValueError("%s: need at least two stations" % who)
+    if not np.all(np.isfinite(raw)):
+        raise ValueError("%s: station coordinates must be finite" % who)
+    v, many = _fields(who, values, n)
+    par = _internal_parameters(who, model, kw.get("variogram_parameters"))
+    scaling, angle = _anisotropy(who, ndim, kw)
+    adj = _adjust(raw, scaling, angle)
+    X = _trend(who, kw.get("drift"), n, adj)
+    reml = bool(kw.get("reml", True))
+    logdet, G = gram(adj, model, par, np.hstack([v, X]))
+    out = nll_from_gram(n, logdet, G, v.shape[1], reml, _pieces(X))
+    return out if many else float(out[0])
+
+
+class MLFit:
+    """What ``fit_variogram_ml`` returns.  ``variogram_parameters`` is the constructor's list form [sill, range, nugget] (FULL sill) and
+    ``anisotropy`` the constructor's anisotropy keywords, so ``OrdinaryKriging(x, y, v, variogram_model=fit.variogram_model,
+    variogram_parameters=fit.variogram_parameters, **fit.anisotropy)`` kriges with the fit.  ``nll`` is the objective at the fit (summed
+    over the fields of (N, F) values), ``n_evaluations`` the device calls spent, ``success`` and ``message`` the optimiser's."""
+
+    def __init__(self, variogram_model, variogram_parameters, anisotropy, nll, n_evaluations, success, message, reml):
+        self.variogram_model = variogram_model
+        self.variogram_parameters = variogram_parameters
+        self.anisotropy = anisotropy
+        for k, val in anisotropy.items():
+            setattr(self, k, val)
+        self.nll = nll
+        self.n_evaluations = n_evaluations
+        self.success = success
+        self.message = message
+        self.reml = reml
+
+    def __repr__(self):
+        return "MLFit(variogram_model=%r, variogram_parameters=%r, anisotropy=%r, nll=%r, n_evaluations=%d, success=%r)" % (
+            self.variogram_model, self.variogram_parameters, self.anisotropy, self.nll, self.n_evaluations, self.success)
+
+
+_FIT_NAMES = ("variogram_model", "start", "fit_anisotropy", "drift", "reml", "bounds")
+NUGGET_FLOOR = 1e-8  # times the variance of the values: the nugget is searched as log(nugget + floor), so that zero is a reachable bound
+
+
+def fit_variogram_ml(x, y, *args, **kwargs):
+    """Maximum-likelihood / REML fit of a bounded variogram model, and optionally of the anisotropy, to the stations -- binning-free.
+
+    ``fit = fit_variogram_ml(x, y[, z], values, variogram_model, start=None, fit_anisotropy=False, drift=None, reml=True, bounds=None,
+    **anisotropy)``
+
+    Minimises ``neg_log_likelihood`` with ``scipy.optimize.minimize(method='Nelder-Mead')``: derivative-free, so a trial model whose
+    matrix is not positive definite (``inf``) does no harm, and deterministic.  One device call per evaluation.  The search is over
+    log psill, log range and log(nugget + floor), floor = 1e-8 var(values), so that nugget = 0 is reachable as a bound; with
+    fit_anisotropy also over log scaling and the angle in degrees (2-D) or the two log scalings and the three angles (3-D).  After the
+    first convergence the search is restarted once from its result with a fresh simplex.
+
+    values: one field (N,), or (N, F) treated as F independent replicates of one variogram -- the objective is the sum over the fields.
+    start: None -- the constructor's least-squares fit of the binned variogram (of the first field) -- or variogram parameters in the
+    constructor's forms.  The anisotropy keywords of the constructor (``anisotropy_scaling``, ``anisotropy_angle``; 3-D:
+    ``anisotropy_scaling_y`` ...) give the fixed anisotropy, or the start of its search.  bounds: a dict from 'psill', 'range', 'nugget',
+    'scaling' to (low, high) in natural units, overriding the defaults (psill and nugget up to 100 var(values), range between 1e-3 and
+    10 times the bounding box's diagonal, scaling in [0.05, 20]; angles are free).  drift and reml as in ``neg_log_likelihood``.
+
+    Returns an ``MLFit``: ``variogram_parameters`` in the constructor's list form, the anisotropy values (``fit.anisotropy`` as
+    keywords), ``nll``, ``n_evaluations``, ``success`` (either pass of the search met its tolerances: 1e-3 in the
+    parameters, 1e-6 in the objective).  Argument errors are raised before the library is loaded."""
+    from scipy.optimize import minimize
+
+    who = "fit_variogram_ml"
+    raw, values, kw = _split(who, (x, y) + args, dict(kwargs), _FIT_NAMES)
+    unknown = set(kw) - set(_FIT_NAMES) - set(_ANIS2) - set(_ANIS3)
+    if unknown:
+        raise TypeError("%s: unexpected argument %s" % (who, ", ".join(sorted(unknown))))
+    if "variogram_model" not in kw:
+        raise TypeError("%s: variogram_model is required" % who)
+    model = kw["variogram_model"]
+    _check_model(who, model)
+    n, ndim = raw.shape
+    if n < 2:
+        raise ValueError("%s: need at least two stations" % who)
+    if not np.all(np.isfinite(raw)):
+        raise ValueError("%s: station coordinates must be finite" % who)
+    v, _ = _fields(who, values, n)
+    scaling0, angle0 = _anisotropy(who, ndim, kw)
+    drift = kw.get("drift")
+    X = _trend(who, drift, n, _adjust(raw, scaling0, angle0))
+    reml = bool(kw.get("reml", True))
+    fit_anis = bool(kw.get("fit_anisotropy", False))
+    var = float(np.var(v))
+    if not var > 0.0:
+        raise ValueError("%s: the values are constant; there is no variogram to fit" % who)
+    diag = float(np.sqrt(np.sum((raw.max(axis=0) - raw.min(axis=0)) ** 2)))
+    if not diag > 0.0:
+        raise ValueError("%s: all stations coincide" % who)
+    floor = NUGGET_FLOOR * var
+    lim = {"psill": (1e-6 * var, 100.0 * var), "range": (1e-3 * diag, 10.0 * diag), "nugget": (0.0, 100.0 * var), "scaling": (0.05, 20.0)}
+    given = kw.get("bounds")
+    if given is not None:
+        if not isinstance(given, dict) or set(given) - set(lim):
+            raise ValueError("%s: bounds must be a dict with keys among 'psill', 'range', 'nugget', 'scaling'" % who)
+        for k, (lo, hi) in given.items():
+            lo, hi = float(lo), float(hi)
+            if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi and (lo > 0.0 or (k == "nugget" and lo >= 0.0))):
+                raise ValueError("%s: bounds[%r] must be (low, high) with 0 < low < high (nugget: 0 <= low)" % (who, k))
+            lim[k] = (lo, hi)
+    start = kw.get("start")
+    if start is None:
+        from . import variogram_fit
+
+        _, _, par0 = variogram_fit.fit(_adjust(raw, scaling0, angle0), v[:, 0], model, 6, False, "euclidean")
+        par0 = [float(t) for t in par0]
+    else:
+        par0 = _internal_parameters(who, model, start)
+    clip = lambda t, k: min(max(t, lim[k][0]), lim[k][1])
+    par0 = [clip(par0[0], "psill"), clip(par0[1], "range"), clip(par0[2], "nugget")]
+    pieces = _pieces(X)
+    moving = isinstance(drift, str) and fit_anis  # the trend columns are the adjusted coordinates: they move with the anisotropy
+    nscale = len(scaling0)
+
+    def unpack(t):
+        par = [math.exp(t[0]), math.exp(t[1]), max(math.exp(t[2]) - floor, 0.0)]
+        if fit_anis:
+            return par, [math.exp(s) for s in t[3:3 + nscale]], [float(a) for a in t[3 + nscale:]]
+        return par, scaling0, angle0
+
+    calls = [0]
+
+    def objective(t):
+        par, sc, an = unpack(t)
+        calls[0] += 1
+        adj = _adjust(raw, sc, an)
+        Xt = np.hstack([np.ones((n, 1)), adj]) if moving else X
+        logdet, G = gram(adj, model, par, np.hstack([v, Xt]))
+        return float(np.sum(nll_from_gram(n, logdet, G, v.shape[1], reml, _pieces(Xt) if moving else pieces)))
+
+    t0 = [math.log(par0[0]), math.log(par0[1]), math.log(par0[2] + floor)]
+    box = [tuple(math.log(b) for b in lim["psill"]), tuple(math.log(b) for b in lim["range"]),
+           (math.log(lim["nugget"][0] + floor), math.log(lim["nugget"][1] + floor))]
+    step = [0.4, 0.4, 0.6]
+    if fit_anis:
+        t0 += [math.log(clip(s, "scaling")) for s in scaling0] + list(angle0)
+        box += [tuple(math.log(b) for b in lim["scaling"])] * nscale + [(None, None)] * len(angle0)
+        step += [0.35] * nscale + [25.0] * len(angle0)
+    t0 = np.array(t0)
+    nll0 = objective(t0)  # the start is a candidate too: the result is never worse than it
+
+    def simplex(c, scale):
+        pts = [np.array(c)]
+        for k, s in enumerate(step):
+            q = np.array(c)
+            q[k] += s * scale if box[k][1] is None or q[k] + s * scale <= box[k][1] else -s * scale
+            pts.append(q)
+        return np.array(pts)
+
+    best_t, best = t0, nll0
+    converged, message = False, ""
+    for scale in (1.0, 0.5):  # the search, and one restart from its result
+        res = minimize(objective, best_t, method="Nelder-Mead", bounds=box,
+                       options=dict(initial_simplex=simplex(best_t, scale), xatol=1e-3, fatol=1e-6, maxfev=200 * len(t0)))
+        converged, message = converged or bool(res.success), str(res.message)
+        if res.fun < best:
+            best_t, best = np.array(res.x), float(res.fun)
+    par, sc, an = unpack(best_t)
+    names = _ANIS2 if ndim == 2 else _ANIS3
+    anis = dict(zip(names, list(sc) + list(an)))
+    return MLFit(model, [par[0] + par[2], par[1], par[2]], anis, best, calls[0], bool(converged and math.isfinite(best)), message, reml)
