@@ -1,4 +1,4 @@
-"""Builds pykrige_amd/libmikrige.so, pykrige_amd/libmikvario.so, pykrige_amd/libmikvario3.so and pykrige_amd/libmiklik.so (HIP, gfx950) in-tree.  `python -m pykrige_amd.build [--force] [-j N]`.
+"""Builds pykrige_amd/libmikrige.so, pykrige_amd/libmikvario.so, pykrige_amd/libmikvario3.so, pykrige_amd/libmiklik.so and pykrige_amd/libmikgrad.so (HIP, gfx950) in-tree.  `python -m pykrige_amd.build [--force] [-j N]`.
 
 The library is ten translation units compiled in parallel (objects under pykrige_amd/csrc/build/, git- and gpurun-ignored) and
 linked into one shared object; only the units whose sources or flags changed are recompiled (the command line of every object is
@@ -23,6 +23,11 @@ tests/test_directional_variogram_host.py, so the 3-D kernels have a shared objec
 libmiklik.so (include/miklik.h: log det C and W^T C^-1 W of a station set under a variogram model, for the ML / REML fit of likelihood.py)
 is a fourth library of one unit, mik_lik.hip, built the same way: the second and third libraries are pinned by their host tests as the
 first is, and the call needs no handle and no inverse.  Nothing is linked between the four.
+
+libmikgrad.so (include/mikgrad.h: the same two numbers and the analytic gradient of the ML / REML objective, for the quasi-Newton fit of
+likelihood.py) is a fifth library of one unit, mik_grad.hip, built the same way: the fourth library's exports and kernel list are pinned by
+tests/test_likelihood_host.py.  Its unit includes mik_k_lik.h, unchanged, and compiles the four elimination kernels into itself; no object
+is linked between the five.
 """
 import os
 import shutil
@@ -42,6 +47,8 @@ OUT_VARIO3 = os.path.join(HERE, "libmikvario3.so")
 API_VARIO3 = os.path.join(ROOT, "include", "mikvario3.h")
 OUT_LIK = os.path.join(HERE, "libmiklik.so")
 API_LIK = os.path.join(ROOT, "include", "miklik.h")
+OUT_GRAD = os.path.join(HERE, "libmikgrad.so")
+API_GRAD = os.path.join(ROOT, "include", "mikgrad.h")
 COMMON = ["mik_host.h", "mik_dev.h"]
 # object name -> (source, extra headers it includes, extra flags)
 UNITS = {
@@ -62,6 +69,8 @@ UNITS_VARIO = {"mik_vario": ("mik_vario.hip", ["mik_k_vario.h"])}
 UNITS_VARIO3 = {"mik_vario3": ("mik_vario3.hip", ["mik_k_vario3.h"])}
 # the fourth library, in the same form
 UNITS_LIK = {"mik_lik": ("mik_lik.hip", ["mik_k_lik.h"])}
+# the fifth library, in the same form; it runs the fourth's elimination kernels, so their header is a dependency
+UNITS_GRAD = {"mik_grad": ("mik_grad.hip", ["mik_k_grad.h", "mik_k_lik.h"])}
 # --offload-compress: the code objects travel zstd-compressed inside the fat binary (16.9 -> 2.3 MB of .so; the HIP runtime unpacks them at load);
 # level 19 instead of the default 3 takes another 3 % off and no measurable compile time (the time is in code generation)
 COMPRESS = ["--offload-compress", "--offload-compression-level=19"]
@@ -120,15 +129,21 @@ def lik_deps(name):
     return [os.path.join(CSRC, f) for f in [src] + hdrs] + [API_LIK]
 
 
+def grad_deps(name):
+    src, hdrs = UNITS_GRAD[name]
+    return [os.path.join(CSRC, f) for f in [src] + hdrs] + [API_GRAD]
+
+
 def up_to_date():
     return (not _stale(OUT, all_sources()) and not _stale(OUT_VARIO, [d for n in UNITS_VARIO for d in vario_deps(n)])
             and not _stale(OUT_VARIO3, [d for n in UNITS_VARIO3 for d in vario3_deps(n)])
-            and not _stale(OUT_LIK, [d for n in UNITS_LIK for d in lik_deps(n)]))
+            and not _stale(OUT_LIK, [d for n in UNITS_LIK for d in lik_deps(n)])
+            and not _stale(OUT_GRAD, [d for n in UNITS_GRAD for d in grad_deps(n)]))
 
 
 def build_library(force=False, verbose=False, jobs=None):
-    """Compile the four C-ABI libraries for gfx950; returns the path of libmikrige.so (OUT; libmikvario.so is OUT_VARIO, libmikvario3.so
-    OUT_VARIO3, libmiklik.so OUT_LIK).
+    """Compile the five C-ABI libraries for gfx950; returns the path of libmikrige.so (OUT; libmikvario.so is OUT_VARIO, libmikvario3.so
+    OUT_VARIO3, libmiklik.so OUT_LIK, libmikgrad.so OUT_GRAD).
     Cross-compiles without a GPU."""
     if not force and up_to_date():
         return OUT
@@ -167,6 +182,11 @@ def _build_locked(force, verbose, jobs):
         obj = os.path.join(OBJ, name + ".o")
         if force or _stale(obj, lik_deps(name), FLAGS):
             todo_lik.append((name, FLAGS, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
+    todo_grad = []
+    for name, (src, _) in UNITS_GRAD.items():
+        obj = os.path.join(OBJ, name + ".o")
+        if force or _stale(obj, grad_deps(name), FLAGS):
+            todo_grad.append((name, FLAGS, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
 
     def run(job):
         name, flags, cmd = job
@@ -196,7 +216,7 @@ def _build_locked(force, verbose, jobs):
 
     todo.sort(key=lambda j: -COST.get(j[0].rstrip("0123456789"), 0))
     with ThreadPoolExecutor(max_workers=jobs or min(len(UNITS), os.cpu_count() or 4)) as ex:
-        list(ex.map(run, todo + todo_vario + todo_vario3 + todo_lik))
+        list(ex.map(run, todo + todo_vario + todo_vario3 + todo_lik + todo_grad))
     # (-s: no static symbol table -- 90 kB; the C ABI and the kernels' host stubs are dynamic symbols, `nm -D` lists them)
     links = []
     if relink or _stale(OUT, all_sources()):
@@ -207,6 +227,8 @@ def _build_locked(force, verbose, jobs):
         links.append((OUT_VARIO3, [os.path.join(OBJ, n + ".o") for n in UNITS_VARIO3], ["-Wl,-s"]))
     if todo_lik or _stale(OUT_LIK, [d for n in UNITS_LIK for d in lik_deps(n)]):
         links.append((OUT_LIK, [os.path.join(OBJ, n + ".o") for n in UNITS_LIK], ["-Wl,-s"]))
+    if todo_grad or _stale(OUT_GRAD, [d for n in UNITS_GRAD for d in grad_deps(n)]):
+        links.append((OUT_GRAD, [os.path.join(OBJ, n + ".o") for n in UNITS_GRAD], ["-Wl,-s"]))
     for out, objs, tail in links:
         link = [cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out + pid] + tail
         if verbose:

@@ -926,6 +926,21 @@ class _KrigingBase:
         par = self._list_parameters() if variogram_parameters is None else variogram_parameters
         return likelihood.neg_log_likelihood(*cols, v, self.variogram_model, par, drift=drift, reml=reml, **anis)
 
+    def neg_log_likelihood_grad(self, variogram_parameters=None, reml=True, **anisotropy):
+        """``nll, grad = obj.neg_log_likelihood_grad(variogram_parameters=None, reml=True, **anisotropy)``: what ``neg_log_likelihood``
+        returns, bit for bit, and its analytic gradient from the same elimination on the GPU (libmikgrad.so).  grad is in natural units
+        in the order of ``pykrige_amd.likelihood.GRAD_NAMES_2D`` / ``GRAD_NAMES_3D``: psill (the partial sill, the nugget held), range,
+        nugget, then this class's anisotropy keywords, angles per degree.  The arguments, the trend (``regional_linear`` on the
+        universal classes; the gradient with the trend columns held is exact, see ``likelihood.neg_log_likelihood_grad``) and the
+        refusals are ``neg_log_likelihood``'s: 'linear', 'power' (ValueError) and 'custom' (NotImplementedError) models,
+        coordinates_type='geographic' and a handle that spans a device group (ValueError), any other drift term
+        (``NotImplementedError``).  A matrix that is not positive definite gives ``inf`` and a gradient of NaN."""
+        from . import likelihood
+
+        cols, v, drift, anis = self._likelihood_problem("neg_log_likelihood_grad", anisotropy)
+        par = self._list_parameters() if variogram_parameters is None else variogram_parameters
+        return likelihood.neg_log_likelihood_grad(*cols, v, self.variogram_model, par, drift=drift, reml=reml, **anis)
+
     def fit_variogram_ml(self, start=None, fit_anisotropy=False, reml=True, bounds=None, **anisotropy):
         """Maximum-likelihood / REML fit of this object's variogram model (and, with fit_anisotropy, of its anisotropy) to its stations
         and values -- binning-free: ``fit = obj.fit_variogram_ml(start=None, fit_anisotropy=False, reml=True, bounds=None, **anisotropy)``.
@@ -934,12 +949,15 @@ class _KrigingBase:
         ``fit.anisotropy`` as the constructor's keywords, ``fit.nll``, ``fit.n_evaluations``, ``fit.success``; the object itself is not
         changed -- hand the fit to ``update_variogram_model`` or to a new object.  The trend and the refusals are those of
         ``neg_log_likelihood``: 'linear', 'power' and 'custom' models, coordinates_type='geographic', a device group, and on the universal
-        classes any drift term but ``regional_linear`` (``NotImplementedError``)."""
+        classes any drift term but ``regional_linear`` (``NotImplementedError``).  ``method='l-bfgs-b'``, given by keyword, is passed
+        on: the quasi-Newton search with the analytic gradient (``likelihood.fit_variogram_ml``); the default is 'nelder-mead'."""
         from . import likelihood
 
+        anisotropy = dict(anisotropy)
+        method = anisotropy.pop("method", "nelder-mead")
         cols, v, drift, anis = self._likelihood_problem("fit_variogram_ml", anisotropy)
         return likelihood.fit_variogram_ml(*cols, v, self.variogram_model, start=self._list_parameters() if start is None else start,
-                                           fit_anisotropy=fit_anisotropy, drift=drift, reml=reml, bounds=bounds, **anis)
+                                           fit_anisotropy=fit_anisotropy, drift=drift, reml=reml, bounds=bounds, method=method, **anis)
 
     def _resident_problem(self, P, name, one_device):
         """The handle with this object's problem set (only if its key changed) and the points P loaded: (handle, factor key).

@@ -344,7 +344,8 @@ class MLFit:
             self.variogram_model, self.variogram_parameters, self.anisotropy, self.nll, self.n_evaluations, self.success)
 
 
-_FIT_NAMES = ("variogram_model", "start", "fit_anisotropy", "drift", "reml", "bounds")
+_FIT_NAMES = ("variogram_model", "start", "fit_anisotropy", "drift", "reml", "bounds", "method")
+FIT_METHODS = ("nelder-mead", "l-bfgs-b")
 NUGGET_FLOOR = 1e-8  # times the variance of the values: the nugget is searched as log(nugget + floor), so that zero is a reachable bound
 
 
@@ -369,7 +370,14 @@ def fit_variogram_ml(x, y, *args, **kwargs):
 
     Returns an ``MLFit``: ``variogram_parameters`` in the constructor's list form, the anisotropy values (``fit.anisotropy`` as
     keywords), ``nll``, ``n_evaluations``, ``success`` (either pass of the search met its tolerances: 1e-3 in the
-    parameters, 1e-6 in the objective).  Argument errors are raised before the library is loaded."""
+    parameters, 1e-6 in the objective).  Argument errors are raised before the library is loaded.
+
+    ``method='nelder-mead'`` (the default) is the search above.  ``method='l-bfgs-b'`` minimises the same objective over the same
+    coordinates and bounds with ``scipy.optimize.minimize(method='L-BFGS-B', jac=True)`` and the analytic gradient of
+    ``neg_log_likelihood_grad`` (libmikgrad.so; one device call returns the value and the gradient), summed over the fields and taken
+    to the search coordinates by the chain rule on the host.  The start is a candidate here too.  A trial that is not positive definite
+    does not raise: the line search is told to back off; if L-BFGS-B cannot finish, the Nelder-Mead search continues from the best point
+    seen and ``message`` says so.  ``n_evaluations`` counts the device calls of both kinds."""
     from scipy.optimize import minimize
 
     who = "fit_variogram_ml"
@@ -392,6 +400,12 @@ def fit_variogram_ml(x, y, *args, **kwargs):
     X = _trend(who, drift, n, _adjust(raw, scaling0, angle0))
     reml = bool(kw.get("reml", True))
     fit_anis = bool(kw.get("fit_anisotropy", False))
+    method = kw.get("method", "nelder-mead")
+    if method is None:
+        method = "nelder-mead"
+    if not isinstance(method, str) or method.lower() not in FIT_METHODS:
+        raise ValueError("%s: method must be one of %s, got %r" % (who, ", ".join(repr(k) for k in FIT_METHODS), method))
+    method = method.lower()
     var = float(np.var(v))
     if not var > 0.0:
         raise ValueError("%s: the values are constant; there is no variogram to fit" % who)
@@ -458,9 +472,25 @@ def fit_variogram_ml(x, y, *args, **kwargs):
             pts.append(q)
         return np.array(pts)
 
+    def value_and_gradient(t):
+        """The objective and its gradient in the search coordinates: one device call."""
+        par, sc, an = unpack(t)
+        calls[0] += 1
+        adj = _adjust(raw, sc, an)
+        Xt = np.hstack([np.ones((n, 1)), adj]) if moving else X
+        dco = anisotropy_derivatives(raw, sc, an) if fit_anis else np.zeros((0, n, ndim))
+        logdet, G, grad, _ = gram_grad(adj, dco, model, par, v, Xt, reml)
+        f = float(np.sum(nll_from_gram(n, logdet, G, v.shape[1], reml, _pieces(Xt) if moving else pieces)))
+        g = np.sum(grad, axis=0)
+        # d/dlog psill, d/dlog range, d/dlog(nugget + floor), d/dlog scaling; the angles are searched in degrees
+        chain = [par[0], par[1], par[2] + floor] + ([float(s_) for s_ in sc] + [1.0] * len(an) if fit_anis else [])
+        return f, g * np.array(chain)
+
     best_t, best = t0, nll0
     converged, message = False, ""
-    for scale in (1.0, 0.5):  # the search, and one restart from its result
+    if method == "l-bfgs-b":
+        best_t, best, converged, message = _fit_lbfgsb(minimize, objective, value_and_gradient, t0, nll0, box, simplex)
+    for scale in (() if method == "l-bfgs-b" else (1.0, 0.5)):  # the search, and one restart from its result
         res = minimize(objective, best_t, method="Nelder-Mead", bounds=box,
                        options=dict(initial_simplex=simplex(best_t, scale), xatol=1e-3, fatol=1e-6, maxfev=200 * len(t0)))
         converged, message = converged or bool(res.success), str(res.message)
@@ -470,3 +500,212 @@ def fit_variogram_ml(x, y, *args, **kwargs):
     names = _ANIS2 if ndim == 2 else _ANIS3
     anis = dict(zip(names, list(sc) + list(an)))
     return MLFit(model, [par[0] + par[2], par[1], par[2]], anis, best, calls[0], bool(converged and math.isfinite(best)), message, reml)
+
+
+# ------------------------------------------------------------------------------------------------------------- the analytic gradient
+# ctypes binding of libmikgrad.so (include/mikgrad.h), a fifth library, loaded on first use of neg_log_likelihood_grad or of
+# fit_variogram_ml(method='l-bfgs-b'); everything above works without it.
+LIB_PATH_GRAD = os.path.join(_HERE, "libmikgrad.so")
+MLG_OK, MLG_EINVAL, MLG_ENOTPD, MLG_EHIP = 0, -1, -2, -3
+ABI_VERSION_GRAD = 1  # include/mikgrad.h MLG_ABI_VERSION
+MAXGEOM = 5  # MLG_MAXGEOM
+GRAD_NAMES_2D = ("psill", "range", "nugget") + _ANIS2
+GRAD_NAMES_3D = ("psill", "range", "nugget") + _ANIS3
+
+# every entry point include/mikgrad.h declares: name -> (restype, argtypes)
+SIGNATURES_GRAD = {
+    "mlg_abi_version": (C.c_int, []),
+    "mlg_last_error": (C.c_char_p, []),
+    "mlg_grad": (C.c_int, [C.c_int, C.c_int64, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, C.c_double, C.c_double, C.c_double, _dp, C.c_int32,
+                           _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, _i32p]),
+}
+
+_lib_grad = None
+
+
+def load_grad():
+    """dlopen libmikgrad.so and declare the signatures.  Raises ImportError if it has not been built or is stale."""
+    global _lib_grad
+    if _lib_grad is not None:
+        return _lib_grad
+    if not os.path.exists(LIB_PATH_GRAD):
+        raise ImportError(
+            "pykrige_amd: %s is missing -- build it with `python -m pykrige_amd.build` "
+            "(needs hipcc; there is no CPU fallback)" % LIB_PATH_GRAD)
+    lib = C.CDLL(LIB_PATH_GRAD)
+    have = getattr(lib, "mlg_abi_version", None)
+    version = None
+    if have is not None:
+        have.restype, have.argtypes = SIGNATURES_GRAD["mlg_abi_version"]
+        version = have()
+    stale = "pykrige_amd: %s %%s, this package was written against ABI version %d -- rebuild it (`python -m pykrige_amd.build --force`)" % (
+        LIB_PATH_GRAD, ABI_VERSION_GRAD)
+    if version != ABI_VERSION_GRAD:
+        raise ImportError(stale % ("has no mlg_abi_version" if version is None else "has ABI version %d" % version))
+    for name, (res, args) in SIGNATURES_GRAD.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise ImportError(stale % ("does not export %s" % name)) from None
+        fn.restype = res
+        fn.argtypes = args
+    _lib_grad = lib
+    return lib
+
+
+def gram_grad(coords, dcoords, model, parameters, V, X, reml):
+    """``logdet, G, grad, info = gram_grad(coords, dcoords, model, parameters, V, X, reml)``: one call of ``mlg_grad``, the one device
+    call of the gradient path.
+
+    coords: (N, 2) or (N, 3) adjusted coordinates; dcoords: (ng, N, ndim), 0 <= ng <= 5, for each geometry parameter the derivative of
+    the adjusted coordinates; parameters: the internal [psill, range, nugget]; V: (N, F) fields, 1 <= F <= 32; X: (N, p) trend columns,
+    1 <= p <= 8.  logdet and G = W^T C^-1 W of W = [V | X] are ``gram``'s bit for bit; grad is (F, 3 + ng): for every field the
+    derivatives of the ML (reml false) or REML objective of ``nll_from_gram`` with respect to psill, range, nugget and the ng geometry
+    parameters, X held fixed.  If C (or X^T C^-1 X) is not positive definite in float64: logdet ``inf``, G and grad NaN, and info the
+    1-based column of the failed pivot (0 otherwise).  The arguments are checked by the callers in this module; there is no CPU
+    fallback."""
+    Xc = np.ascontiguousarray(np.asarray(coords, dtype=np.float64))
+    n, ndim = Xc.shape
+    D = np.ascontiguousarray(np.asarray(dcoords, dtype=np.float64).reshape(-1, n, ndim).transpose(0, 2, 1))
+    ng = int(D.shape[0])
+    psill, rng, nugget = (float(t) for t in parameters)
+    Va, Xa = np.asarray(V, dtype=np.float64), np.asarray(X, dtype=np.float64)
+    F, p = int(Va.shape[1]), int(Xa.shape[1])
+    ct, vt, xt = np.ascontiguousarray(Xc.T), np.ascontiguousarray(Va.T), np.ascontiguousarray(Xa.T)
+    m = F + p
+    G = np.zeros((m, m))
+    grad = np.zeros((F, 3 + ng))
+    logdet = C.c_double(0.0)
+    info = C.c_int32(0)
+    lib = load_grad()
+    rc = lib.mlg_grad(_device(), n, ndim, ct.ctypes.data_as(_dp), ng, D.ctypes.data_as(_dp) if ng else None, MODEL_IDS[model], psill, rng,
+                      nugget, vt.ctypes.data_as(_dp), F, xt.ctypes.data_as(_dp), p, 1 if reml else 0, C.byref(logdet), G.ctypes.data_as(_dp),
+                      grad.ctypes.data_as(_dp), C.byref(info))
+    if rc == MLG_ENOTPD:
+        return math.inf, np.full((m, m), np.nan), np.full((F, 3 + ng), np.nan), int(info.value)
+    if rc != MLG_OK:
+        msg = (lib.mlg_last_error() or b"").decode("utf-8", "replace")
+        if rc == MLG_EINVAL:
+            raise ValueError(msg)
+        raise RuntimeError("libmikgrad: %s (code %d)" % (msg, rc))
+    return float(logdet.value), G, grad, 0
+
+
+def anisotropy_derivatives(raw, scaling, angle):
+    """(ng, N, ndim): for each anisotropy parameter -- 2-D: scaling, angle; 3-D: scaling_y, scaling_z, angle_x, angle_y, angle_z -- the
+    derivative of ``core.adjust_for_anisotropy(raw, centre, scaling, angle)`` with respect to it, angles per degree: the derivative of
+    ``stretch . rot`` (``core.anisotropy_matrices``) applied to the raw coordinates about the constructor's centre.  The centre cancels
+    in every difference of two stations."""
+    raw = np.asarray(raw, dtype=np.float64)
+    ndim = raw.shape[1]
+    center = np.array([(float(np.amax(c)) + float(np.amin(c))) / 2.0 for c in raw.T])
+    Y = (raw - center[None, :]).T
+    rot, stretch = core.anisotropy_matrices(ndim, scaling, angle)
+    S = np.diag(stretch)
+    k = -np.pi / 180.0  # the rotations are built from -angle in radians
+    ang = np.asarray(angle, dtype=np.float64) * np.pi / 180
+    if ndim == 2:
+        c, s = np.cos(-ang[0]), np.sin(-ang[0])
+        mats = [np.diag([0.0, 1.0]) @ rot, S @ (k * np.array([[-s, -c], [c, -s]]))]
+    else:
+        cx, sx = np.cos(-ang[0]), np.sin(-ang[0])
+        cy, sy = np.cos(-ang[1]), np.sin(-ang[1])
+        cz, sz = np.cos(-ang[2]), np.sin(-ang[2])
+        rot_x = np.array([[1.0, 0.0, 0.0], [0.0, cx, -sx], [0.0, sx, cx]])
+        rot_y = np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]])
+        rot_z = np.array([[cz, -sz, 0.0], [sz, cz, 0.0], [0.0, 0.0, 1.0]])
+        d_x = k * np.array([[0.0, 0.0, 0.0], [0.0, -sx, -cx], [0.0, cx, -sx]])
+        d_y = k * np.array([[-sy, 0.0, cy], [0.0, 0.0, 0.0], [-cy, 0.0, -sy]])
+        d_z = k * np.array([[-sz, -cz, 0.0], [cz, -sz, 0.0], [0.0, 0.0, 0.0]])
+        mats = [np.diag([0.0, 1.0, 0.0]) @ rot, np.diag([0.0, 0.0, 1.0]) @ rot, S @ rot_z @ rot_y @ d_x, S @ rot_z @ d_y @ rot_x,
+                S @ d_z @ rot_y @ rot_x]
+    return np.array([(M @ Y).T for M in mats])
+
+
+def neg_log_likelihood_grad(x, y, *args, **kwargs):
+    """The negative Gaussian log-likelihood of ``neg_log_likelihood`` and its analytic gradient, from one elimination on the GPU.
+
+    ``nll, grad = neg_log_likelihood_grad(x, y[, z], values, variogram_model, variogram_parameters, anisotropy_scaling=1.0,
+    anisotropy_angle=0.0, drift=None, reml=True)`` -- the arguments of ``neg_log_likelihood``.  nll is what ``neg_log_likelihood``
+    returns, bit for bit.  grad has shape (3 + ng,) for (N,) values and (F, 3 + ng) for (N, F) values, in natural units and in the
+    order of ``GRAD_NAMES_2D`` / ``GRAD_NAMES_3D``: psill (the PARTIAL sill, with the nugget held), range, nugget, then the
+    constructor's anisotropy keywords (ng = 2 in the plane, 5 in space), angles per degree.  Row f of an (N, F) call is bit for bit the
+    one-field call.
+
+    d nll / d theta_k = 1/2 tr(M dC/dtheta_k) - 1/2 a^T (dC/dtheta_k) a with a = P y, P = Q - Q X (X^T Q X)^-1 X^T Q, Q = C^-1, and
+    M = P under REML, Q under ML; the derivative matrices are defined in include/mikgrad.h.  The host forms the derivatives of the
+    adjusted coordinates analytically (``anisotropy_derivatives``).  With drift='regional_linear' the trend columns move with the
+    anisotropy, but the objective depends on X only through its column space (-log det X^T X + log det X^T Q X is invariant under
+    X -> X A), and the column space of [1 | adjusted coordinates] is that of [1 | raw coordinates] for every anisotropy: the gradient
+    taken with X held at the current adjusted coordinates is exact.
+
+    A covariance matrix that is not positive definite in float64 gives ``inf`` and a gradient of NaN.  The refusals are
+    ``neg_log_likelihood``'s, raised before the library is loaded.  There is no CPU fallback."""
+    who = "neg_log_likelihood_grad"
+    raw, values, kw = _split(who, (x, y) + args, dict(kwargs), _NLL_NAMES)
+    unknown = set(kw) - set(_NLL_NAMES) - set(_ANIS2) - set(_ANIS3) - {"drift", "reml"}
+    if unknown:
+        raise TypeError("%s: unexpected argument %s" % (who, ", ".join(sorted(unknown))))
+    if "variogram_model" not in kw:
+        raise TypeError("%s: variogram_model is required" % who)
+    model = kw["variogram_model"]
+    _check_model(who, model)
+    n, ndim = raw.shape
+    if n < 2:
+        raise ValueError("%s: need at least two stations" % who)
+    if not np.all(np.isfinite(raw)):
+        raise ValueError("%s: station coordinates must be finite" % who)
+    v, many = _fields(who, values, n)
+    par = _internal_parameters(who, model, kw.get("variogram_parameters"))
+    scaling, angle = _anisotropy(who, ndim, kw)
+    adj = _adjust(raw, scaling, angle)
+    X = _trend(who, kw.get("drift"), n, adj)
+    reml = bool(kw.get("reml", True))
+    logdet, G, grad, _ = gram_grad(adj, anisotropy_derivatives(raw, scaling, angle), model, par, v, X, reml)
+    out = nll_from_gram(n, logdet, G, v.shape[1], reml, _pieces(X))
+    return (out, grad) if many else (float(out[0]), grad[0])
+
+
+def _fit_lbfgsb(minimize, objective, value_and_gradient, t0, nll0, box, simplex):
+    """The quasi-Newton search of fit_variogram_ml(method='l-bfgs-b'): (best t, best nll, converged, message).  A trial whose matrix is
+    not positive definite is answered with a finite value above everything seen and a zero gradient, so that the line search backs off;
+    if L-BFGS-B still cannot finish, the Nelder-Mead search continues from the best point seen.
+
+    The nugget is searched as log(nugget + floor): where the nugget is far below the partial sill that coordinate is a plateau -- its
+    gradient is (nugget + floor) d nll / d nugget, next to nothing whatever the natural derivative says -- and a start with nugget = 0
+    (the least-squares fit gives it often) sits on the bound.  So after a pass that ends with nugget < psill / 1000 and
+    d nll / d nugget < 0, the search is run once more from its result with the nugget lifted to psill / 100; the best point seen wins."""
+    best = [np.array(t0), float(nll0), None]
+    worst = [float(nll0)]
+    refused = set()  # the trials that were answered with the stand-in value
+
+    def fun(t):
+        f, g = value_and_gradient(t)
+        if not (math.isfinite(f) and np.all(np.isfinite(g))):
+            refused.add(tuple(float(c) for c in t))
+            return worst[0] + 1e3 * (1.0 + abs(worst[0])), np.zeros(len(t))
+        worst[0] = max(worst[0], f)
+        if f < best[1] or best[2] is None:
+            best[0], best[1], best[2] = np.array(t), min(f, best[1]), np.array(g)
+        return f, g
+
+    opts = dict(maxiter=200, maxfun=400, ftol=1e-10, gtol=1e-6)
+    res = minimize(fun, np.array(t0), method="L-BFGS-B", jac=True, bounds=box, options=opts)
+    lifted = float(np.log(1e-2 * math.exp(best[0][0]) + math.exp(box[2][0])))  # (exp of the lower bound of t[2] is nugget_low + floor)
+    if best[2] is not None and best[2][2] < 0.0 and math.exp(best[0][2]) - math.exp(box[2][0]) < 1e-3 * math.exp(best[0][0]) \
+            and box[2][0] < lifted < box[2][1]:
+        t1 = np.array(best[0])
+        t1[2] = lifted
+        again = minimize(fun, t1, method="L-BFGS-B", jac=True, bounds=box, options=opts)
+        if again.fun <= res.fun:
+            res = again
+    message = str(res.message.decode() if isinstance(res.message, bytes) else res.message)
+    converged = bool(res.success) and tuple(float(c) for c in res.x) not in refused  # (a zero gradient there is no convergence)
+    if not converged:
+        res = minimize(objective, best[0], method="Nelder-Mead", bounds=box,
+                       options=dict(initial_simplex=simplex(best[0], 0.5), xatol=1e-3, fatol=1e-6, maxfev=200 * len(t0)))
+        message = "L-BFGS-B could not continue (%s); finished with the Nelder-Mead search from the best point: %s" % (message, res.message)
+        converged = bool(res.success)
+        if res.fun < best[1]:
+            best[0], best[1] = np.array(res.x), float(res.fun)
+    return best[0], best[1], converged, message
