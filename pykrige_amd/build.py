@@ -1,4 +1,4 @@
-"""Builds pykrige_amd/libmikrige.so, pykrige_amd/libmikvario.so, pykrige_amd/libmikvario3.so, pykrige_amd/libmiklik.so and pykrige_amd/libmikgrad.so (HIP, gfx950) in-tree.  `python -m pykrige_amd.build [--force] [-j N]`.
+"""Builds pykrige_amd/libmikrige.so, pykrige_amd/libmikvario.so, pykrige_amd/libmikvario3.so, pykrige_amd/libmiklik.so, pykrige_amd/libmikgrad.so and pykrige_amd/libmikvecchia.so (HIP, gfx950) in-tree.  `python -m pykrige_amd.build [--force] [-j N]`.
 
 The library is ten translation units compiled in parallel (objects under pykrige_amd/csrc/build/, git- and gpurun-ignored) and
 linked into one shared object; only the units whose sources or flags changed are recompiled (the command line of every object is
@@ -28,6 +28,11 @@ libmikgrad.so (include/mikgrad.h: the same two numbers and the analytic gradient
 likelihood.py) is a fifth library of one unit, mik_grad.hip, built the same way: the fourth library's exports and kernel list are pinned by
 tests/test_likelihood_host.py.  Its unit includes mik_k_lik.h, unchanged, and compiles the four elimination kernels into itself; no object
 is linked between the five.
+
+libmikvecchia.so (include/mikvecchia.h: log det and W^T C^-1 W under Vecchia's approximation -- every station conditioned on at most m
+earlier ones -- for the ML / REML fit of vecchia.py past the N x N matrix) is a sixth library of one unit, mik_vecchia.hip, built the same
+way: the fourth and fifth libraries' exports and kernel lists are pinned by their host tests.  Its unit includes its own header only;
+nothing is linked between the six.
 """
 import os
 import shutil
@@ -49,6 +54,8 @@ OUT_LIK = os.path.join(HERE, "libmiklik.so")
 API_LIK = os.path.join(ROOT, "include", "miklik.h")
 OUT_GRAD = os.path.join(HERE, "libmikgrad.so")
 API_GRAD = os.path.join(ROOT, "include", "mikgrad.h")
+OUT_VECCHIA = os.path.join(HERE, "libmikvecchia.so")
+API_VECCHIA = os.path.join(ROOT, "include", "mikvecchia.h")
 COMMON = ["mik_host.h", "mik_dev.h"]
 # object name -> (source, extra headers it includes, extra flags)
 UNITS = {
@@ -71,6 +78,8 @@ UNITS_VARIO3 = {"mik_vario3": ("mik_vario3.hip", ["mik_k_vario3.h"])}
 UNITS_LIK = {"mik_lik": ("mik_lik.hip", ["mik_k_lik.h"])}
 # the fifth library, in the same form; it runs the fourth's elimination kernels, so their header is a dependency
 UNITS_GRAD = {"mik_grad": ("mik_grad.hip", ["mik_k_grad.h", "mik_k_lik.h"])}
+# the sixth library, in the same form
+UNITS_VECCHIA = {"mik_vecchia": ("mik_vecchia.hip", ["mik_k_vecchia.h"])}
 # --offload-compress: the code objects travel zstd-compressed inside the fat binary (16.9 -> 2.3 MB of .so; the HIP runtime unpacks them at load);
 # level 19 instead of the default 3 takes another 3 % off and no measurable compile time (the time is in code generation)
 COMPRESS = ["--offload-compress", "--offload-compression-level=19"]
@@ -134,16 +143,22 @@ def grad_deps(name):
     return [os.path.join(CSRC, f) for f in [src] + hdrs] + [API_GRAD]
 
 
+def vecchia_deps(name):
+    src, hdrs = UNITS_VECCHIA[name]
+    return [os.path.join(CSRC, f) for f in [src] + hdrs] + [API_VECCHIA]
+
+
 def up_to_date():
     return (not _stale(OUT, all_sources()) and not _stale(OUT_VARIO, [d for n in UNITS_VARIO for d in vario_deps(n)])
             and not _stale(OUT_VARIO3, [d for n in UNITS_VARIO3 for d in vario3_deps(n)])
             and not _stale(OUT_LIK, [d for n in UNITS_LIK for d in lik_deps(n)])
-            and not _stale(OUT_GRAD, [d for n in UNITS_GRAD for d in grad_deps(n)]))
+            and not _stale(OUT_GRAD, [d for n in UNITS_GRAD for d in grad_deps(n)])
+            and not _stale(OUT_VECCHIA, [d for n in UNITS_VECCHIA for d in vecchia_deps(n)]))
 
 
 def build_library(force=False, verbose=False, jobs=None):
-    """Compile the five C-ABI libraries for gfx950; returns the path of libmikrige.so (OUT; libmikvario.so is OUT_VARIO, libmikvario3.so
-    OUT_VARIO3, libmiklik.so OUT_LIK, libmikgrad.so OUT_GRAD).
+    """Compile the six C-ABI libraries for gfx950; returns the path of libmikrige.so (OUT; libmikvario.so is OUT_VARIO, libmikvario3.so
+    OUT_VARIO3, libmiklik.so OUT_LIK, libmikgrad.so OUT_GRAD, libmikvecchia.so OUT_VECCHIA).
     Cross-compiles without a GPU."""
     if not force and up_to_date():
         return OUT
@@ -187,6 +202,11 @@ def _build_locked(force, verbose, jobs):
         obj = os.path.join(OBJ, name + ".o")
         if force or _stale(obj, grad_deps(name), FLAGS):
             todo_grad.append((name, FLAGS, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
+    todo_vecchia = []
+    for name, (src, _) in UNITS_VECCHIA.items():
+        obj = os.path.join(OBJ, name + ".o")
+        if force or _stale(obj, vecchia_deps(name), FLAGS):
+            todo_vecchia.append((name, FLAGS, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
 
     def run(job):
         name, flags, cmd = job
@@ -216,7 +236,7 @@ def _build_locked(force, verbose, jobs):
 
     todo.sort(key=lambda j: -COST.get(j[0].rstrip("0123456789"), 0))
     with ThreadPoolExecutor(max_workers=jobs or min(len(UNITS), os.cpu_count() or 4)) as ex:
-        list(ex.map(run, todo + todo_vario + todo_vario3 + todo_lik + todo_grad))
+        list(ex.map(run, todo + todo_vecchia + todo_vario + todo_vario3 + todo_lik + todo_grad))
     # (-s: no static symbol table -- 90 kB; the C ABI and the kernels' host stubs are dynamic symbols, `nm -D` lists them)
     links = []
     if relink or _stale(OUT, all_sources()):
@@ -229,6 +249,8 @@ def _build_locked(force, verbose, jobs):
         links.append((OUT_LIK, [os.path.join(OBJ, n + ".o") for n in UNITS_LIK], ["-Wl,-s"]))
     if todo_grad or _stale(OUT_GRAD, [d for n in UNITS_GRAD for d in grad_deps(n)]):
         links.append((OUT_GRAD, [os.path.join(OBJ, n + ".o") for n in UNITS_GRAD], ["-Wl,-s"]))
+    if todo_vecchia or _stale(OUT_VECCHIA, [d for n in UNITS_VECCHIA for d in vecchia_deps(n)]):
+        links.append((OUT_VECCHIA, [os.path.join(OBJ, n + ".o") for n in UNITS_VECCHIA], ["-Wl,-s"]))
     for out, objs, tail in links:
         link = [cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out + pid] + tail
         if verbose:

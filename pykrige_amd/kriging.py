@@ -959,6 +959,37 @@ class _KrigingBase:
         return likelihood.fit_variogram_ml(*cols, v, self.variogram_model, start=self._list_parameters() if start is None else start,
                                            fit_anisotropy=fit_anisotropy, drift=drift, reml=reml, bounds=bounds, method=method, **anis)
 
+    # ---------------------------------------------------------------- Vecchia's approximation of it (libmikvecchia.so, vecchia.py)
+    def neg_log_likelihood_vecchia(self, variogram_parameters=None, m=30, order="random", seed=0, plan=None, reml=True, **anisotropy):
+        """``neg_log_likelihood`` in Vecchia's approximation, for station sets past the N x N matrix:
+        ``nll = obj.neg_log_likelihood_vecchia(variogram_parameters=None, m=30, order="random", seed=0, plan=None, reml=True,
+        **anisotropy)``.  Every station is conditioned on its m nearest predecessors in the order (``pykrige_amd.vecchia.VecchiaPlan``);
+        with m >= N - 1 the value is the exact likelihood.  plan: a ``VecchiaPlan`` of this object's adjusted stations to reuse, else one
+        is built and dropped.  The parameters, the anisotropy overrides, the trend (``regional_linear`` on the universal classes) and the
+        refusals are ``neg_log_likelihood``'s: 'linear', 'power' (ValueError) and 'custom' (NotImplementedError) models,
+        coordinates_type='geographic' and a handle that spans a device group (ValueError), any other drift term
+        (``NotImplementedError``) -- all before anything is loaded."""
+        from . import vecchia
+
+        cols, v, drift, anis = self._likelihood_problem("neg_log_likelihood_vecchia", anisotropy)
+        par = self._list_parameters() if variogram_parameters is None else variogram_parameters
+        return vecchia.neg_log_likelihood_vecchia(*cols, v, self.variogram_model, par, m=m, order=order, seed=seed, plan=plan, drift=drift,
+                                                  reml=reml, **anis)
+
+    def fit_variogram_vecchia(self, m=30, order="random", seed=0, start=None, fit_anisotropy=False, reml=True, bounds=None, **anisotropy):
+        """``fit_variogram_ml`` on Vecchia's objective: ``fit = obj.fit_variogram_vecchia(m=30, order="random", seed=0, start=None,
+        fit_anisotropy=False, reml=True, bounds=None, **anisotropy)``.  One ``VecchiaPlan`` built in the start metric serves the whole
+        Nelder-Mead search (``pykrige_amd.vecchia.fit_variogram_vecchia``); there is no gradient method.  start=None begins at the
+        object's current parameters and anisotropy.  Returns ``pykrige_amd.likelihood.MLFit``; the object itself is not changed.  The
+        trend (``regional_linear``) and the refusals are those of ``neg_log_likelihood``: 'linear', 'power' and 'custom' models,
+        coordinates_type='geographic', a device group, and any other drift term (``NotImplementedError``)."""
+        from . import vecchia
+
+        cols, v, drift, anis = self._likelihood_problem("fit_variogram_vecchia", anisotropy)
+        return vecchia.fit_variogram_vecchia(*cols, v, self.variogram_model, m=m, order=order, seed=seed,
+                                             start=self._list_parameters() if start is None else start, fit_anisotropy=fit_anisotropy,
+                                             drift=drift, reml=reml, bounds=bounds, **anis)
+
     def _resident_problem(self, P, name, one_device):
         """The handle with this object's problem set (only if its key changed) and the points P loaded: (handle, factor key).
         _upload_and_factor without its factor(): mik_predict_cov / mik_predict_block refuse (an oversized P among the reasons) before
