@@ -8,6 +8,8 @@ import os
 
 import numpy as np
 
+from . import _dl
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (MIK_LIB_PATH: a developer switch for A/B runs of two builds on one GPU box; the product loads the in-tree library)
 LIB_PATH = os.environ.get("MIK_LIB_PATH") or os.path.join(_HERE, "libmikrige.so")
@@ -132,32 +134,9 @@ SIGNATURES = {
 def load():
     """dlopen the library and declare the signatures.  Raises if it has not been built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            "pykrige_amd: %s is missing -- build it with `python -m pykrige_amd.build` "
-            "(needs hipcc; there is no CPU fallback)" % LIB_PATH)
-    lib = C.CDLL(LIB_PATH)
-    # the version first: a library from before a symbol was added must end in the "rebuild it" message, not in a bare AttributeError
-    have = getattr(lib, "mik_abi_version", None)
-    version = None
-    if have is not None:
-        have.restype, have.argtypes = SIGNATURES["mik_abi_version"]
-        version = have()
-    stale = "pykrige_amd: %s %%s, this package was written against ABI version %d -- rebuild it (`python -m pykrige_amd.build --force`)" % (
-        LIB_PATH, ABI_VERSION)
-    if version != ABI_VERSION:
-        raise ImportError(stale % ("has no mik_abi_version" if version is None else "has ABI version %d" % version))
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % ("does not export %s" % name)) from None
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _dl.open_library(LIB_PATH, "mik", ABI_VERSION, SIGNATURES)
+    return _lib
 
 
 def last_error():
@@ -167,12 +146,9 @@ def last_error():
 def check(rc):
     if rc == MIK_OK:
         return
-    msg = last_error()
-    if rc == MIK_EINVAL:
-        raise ValueError(msg)
     if rc == MIK_ESINGULAR:
-        raise np.linalg.LinAlgError(msg or "singular matrix")
-    raise RuntimeError("libmikrige: %s (code %d)" % (msg, rc))
+        raise np.linalg.LinAlgError(last_error() or "singular matrix")
+    _dl.raise_for(load(), "mik", "libmikrige", rc, MIK_EINVAL)
 
 
 def _f64(a):
@@ -202,7 +178,7 @@ class Handle:
     def __init__(self, device=None):
         lib = load()
         if device is None:
-            device = int(os.environ.get("MIK_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+            device = _dl.device()
             if lib.mik_device_count() == 1:
                 device = 0
         self._lib = lib

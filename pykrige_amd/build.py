@@ -12,27 +12,17 @@ the whole build holds an flock on csrc/build/.lock, and objects / the library ar
     mik_mw_solve.hip  moving window: the register classes of the pivoting Gauss-Jordan solver (the LDL^T kernels' fallback)
     mik_mw_chol.hip   x 5 (-DMIK_MWC_PART=0..4): the register-tile classes of the moving window's LDL^T solver
 
-libmikvario.so (include/mikvario.h: directional semivariograms and variogram maps) is a second library of one unit, mik_vario.hip, built
-after the first with the same flags under the same lock and rename discipline.  It exists because libmikrige.so is held to a size bar and
-a frozen kernel list (tests/test_abi_and_host.py): new device features go here.  Nothing of it is linked into libmikrige.so or the reverse.
+Five further libraries of one unit each are built after the first with the same flags under the same lock and rename discipline:
+libmikvario.so (mik_vario.hip, include/mikvario.h: directional semivariograms and variogram maps), libmikvario3.so (mik_vario3.hip,
+include/mikvario3.h: the same tools for the 3-D classes), libmiklik.so (mik_lik.hip, include/miklik.h: log det C and W^T C^-1 W for the
+ML / REML fit of likelihood.py), libmikgrad.so (mik_grad.hip, include/mikgrad.h: the same two numbers and the analytic gradient; its unit
+includes mik_k_lik.h, unchanged, and compiles the four elimination kernels into itself) and libmikvecchia.so (mik_vecchia.hip,
+include/mikvecchia.h: the same two numbers under Vecchia's approximation, for vecchia.py).  They exist because libmikrige.so is held to a
+size bar and a frozen kernel list (tests/test_abi_and_host.py), and each later library's exports and kernels are pinned by its own host
+test: new device features get a shared object of their own.  Each unit includes its own headers only, and no object is linked between
+the six.
 
-libmikvario3.so (include/mikvario3.h: the same tools for the 3-D classes -- directions by unit vector, maps of lag-vector cells in x, y, z)
-is a third library of one unit, mik_vario3.hip, built the same way.  The second library's exports and kernels are pinned by
-tests/test_directional_variogram_host.py, so the 3-D kernels have a shared object of their own; nothing is linked between the three.
-
-libmiklik.so (include/miklik.h: log det C and W^T C^-1 W of a station set under a variogram model, for the ML / REML fit of likelihood.py)
-is a fourth library of one unit, mik_lik.hip, built the same way: the second and third libraries are pinned by their host tests as the
-first is, and the call needs no handle and no inverse.  Nothing is linked between the four.
-
-libmikgrad.so (include/mikgrad.h: the same two numbers and the analytic gradient of the ML / REML objective, for the quasi-Newton fit of
-likelihood.py) is a fifth library of one unit, mik_grad.hip, built the same way: the fourth library's exports and kernel list are pinned by
-tests/test_likelihood_host.py.  Its unit includes mik_k_lik.h, unchanged, and compiles the four elimination kernels into itself; no object
-is linked between the five.
-
-libmikvecchia.so (include/mikvecchia.h: log det and W^T C^-1 W under Vecchia's approximation -- every station conditioned on at most m
-earlier ones -- for the ML / REML fit of vecchia.py past the N x N matrix) is a sixth library of one unit, mik_vecchia.hip, built the same
-way: the fourth and fifth libraries' exports and kernel lists are pinned by their host tests.  Its unit includes its own header only;
-nothing is linked between the six.
+LIBRARIES is the one table of all this: a library is one record of it, and a binding module that calls _dl.open_library.
 """
 import os
 import shutil
@@ -44,18 +34,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
-OUT = os.path.join(HERE, "libmikrige.so")
-OUT_VARIO = os.path.join(HERE, "libmikvario.so")
-API = os.path.join(ROOT, "include", "mikrige.h")
-API_VARIO = os.path.join(ROOT, "include", "mikvario.h")
-OUT_VARIO3 = os.path.join(HERE, "libmikvario3.so")
-API_VARIO3 = os.path.join(ROOT, "include", "mikvario3.h")
-OUT_LIK = os.path.join(HERE, "libmiklik.so")
-API_LIK = os.path.join(ROOT, "include", "miklik.h")
-OUT_GRAD = os.path.join(HERE, "libmikgrad.so")
-API_GRAD = os.path.join(ROOT, "include", "mikgrad.h")
-OUT_VECCHIA = os.path.join(HERE, "libmikvecchia.so")
-API_VECCHIA = os.path.join(ROOT, "include", "mikvecchia.h")
 COMMON = ["mik_host.h", "mik_dev.h"]
 # object name -> (source, extra headers it includes, extra flags)
 UNITS = {
@@ -70,16 +48,49 @@ UNITS = {
     "mik_mw_chol3": ("mik_mw_chol.hip", ["mik_k_mw_chol.h"], ["-DMIK_MWC_PART=3"]),
     "mik_mw_chol4": ("mik_mw_chol.hip", ["mik_k_mw_chol.h"], ["-DMIK_MWC_PART=4"]),
 }
-# the second library: object name -> (source, headers it includes); its own headers only, so a change of the first library's leaves it alone
+# the later libraries: object name -> (source, headers it includes); their own headers only, so a change of the first library's leaves them
+# alone.  (The fifth runs the fourth's elimination kernels, so their header is a dependency.)
 UNITS_VARIO = {"mik_vario": ("mik_vario.hip", ["mik_k_vario.h"])}
-# the third library, in the same form
 UNITS_VARIO3 = {"mik_vario3": ("mik_vario3.hip", ["mik_k_vario3.h"])}
-# the fourth library, in the same form
 UNITS_LIK = {"mik_lik": ("mik_lik.hip", ["mik_k_lik.h"])}
-# the fifth library, in the same form; it runs the fourth's elimination kernels, so their header is a dependency
 UNITS_GRAD = {"mik_grad": ("mik_grad.hip", ["mik_k_grad.h", "mik_k_lik.h"])}
-# the sixth library, in the same form
 UNITS_VECCHIA = {"mik_vecchia": ("mik_vecchia.hip", ["mik_k_vecchia.h"])}
+
+
+class Library:
+    """One shared object: its path, its API header, its units, the headers every unit includes and the end of its link line."""
+
+    def __init__(self, name, header, units, common=(), tail=("-Wl,-s",)):
+        self.out = os.path.join(HERE, name)
+        self.api = os.path.join(ROOT, "include", header)
+        self.units, self.common, self.tail = units, list(common), list(tail)
+
+    def deps(self, name):
+        src, hdrs = self.units[name][:2]
+        return [os.path.join(CSRC, f) for f in [src] + hdrs + self.common] + [self.api]
+
+    def sources(self):
+        seen = []
+        for name in self.units:
+            for d in self.deps(name):
+                if d not in seen:
+                    seen.append(d)
+        return seen
+
+
+# (-s: no static symbol table -- 90 kB; the C ABI and the kernels' host stubs are dynamic symbols, `nm -D` lists them)
+LIBRARIES = [
+    Library("libmikrige.so", "mikrige.h", UNITS, COMMON, ["-ldl", "-Wl,-s"]),
+    Library("libmikvario.so", "mikvario.h", UNITS_VARIO),
+    Library("libmikvario3.so", "mikvario3.h", UNITS_VARIO3),
+    Library("libmiklik.so", "miklik.h", UNITS_LIK),
+    Library("libmikgrad.so", "mikgrad.h", UNITS_GRAD),
+    Library("libmikvecchia.so", "mikvecchia.h", UNITS_VECCHIA),
+]
+OUT, OUT_VARIO, OUT_VARIO3, OUT_LIK, OUT_GRAD, OUT_VECCHIA = (lib.out for lib in LIBRARIES)
+API, API_VARIO, API_VARIO3, API_LIK, API_GRAD, API_VECCHIA = (lib.api for lib in LIBRARIES)
+unit_deps, vario_deps, vario3_deps, lik_deps, grad_deps, vecchia_deps = (lib.deps for lib in LIBRARIES)
+all_sources = LIBRARIES[0].sources
 # --offload-compress: the code objects travel zstd-compressed inside the fat binary (16.9 -> 2.3 MB of .so; the HIP runtime unpacks them at load);
 # level 19 instead of the default 3 takes another 3 % off and no measurable compile time (the time is in code generation)
 COMPRESS = ["--offload-compress", "--offload-compression-level=19"]
@@ -93,20 +104,6 @@ def hipcc():
         if c and os.path.exists(c):
             return c
     raise RuntimeError("hipcc not found (need ROCm; set HIPCC=/path/to/hipcc)")
-
-
-def unit_deps(name):
-    src, hdrs, _ = UNITS[name]
-    return [os.path.join(CSRC, f) for f in [src] + hdrs + COMMON] + [API]
-
-
-def all_sources():
-    seen = []
-    for name in UNITS:
-        for d in unit_deps(name):
-            if d not in seen:
-                seen.append(d)
-    return seen
 
 
 def _stale(target, deps, flags=None):
@@ -123,37 +120,8 @@ def _stale(target, deps, flags=None):
     return False
 
 
-def vario_deps(name):
-    src, hdrs = UNITS_VARIO[name]
-    return [os.path.join(CSRC, f) for f in [src] + hdrs] + [API_VARIO]
-
-
-def vario3_deps(name):
-    src, hdrs = UNITS_VARIO3[name]
-    return [os.path.join(CSRC, f) for f in [src] + hdrs] + [API_VARIO3]
-
-
-def lik_deps(name):
-    src, hdrs = UNITS_LIK[name]
-    return [os.path.join(CSRC, f) for f in [src] + hdrs] + [API_LIK]
-
-
-def grad_deps(name):
-    src, hdrs = UNITS_GRAD[name]
-    return [os.path.join(CSRC, f) for f in [src] + hdrs] + [API_GRAD]
-
-
-def vecchia_deps(name):
-    src, hdrs = UNITS_VECCHIA[name]
-    return [os.path.join(CSRC, f) for f in [src] + hdrs] + [API_VECCHIA]
-
-
 def up_to_date():
-    return (not _stale(OUT, all_sources()) and not _stale(OUT_VARIO, [d for n in UNITS_VARIO for d in vario_deps(n)])
-            and not _stale(OUT_VARIO3, [d for n in UNITS_VARIO3 for d in vario3_deps(n)])
-            and not _stale(OUT_LIK, [d for n in UNITS_LIK for d in lik_deps(n)])
-            and not _stale(OUT_GRAD, [d for n in UNITS_GRAD for d in grad_deps(n)])
-            and not _stale(OUT_VECCHIA, [d for n in UNITS_VECCHIA for d in vecchia_deps(n)]))
+    return not any(_stale(lib.out, lib.sources()) for lib in LIBRARIES)
 
 
 def build_library(force=False, verbose=False, jobs=None):
@@ -175,38 +143,16 @@ def build_library(force=False, verbose=False, jobs=None):
 def _build_locked(force, verbose, jobs):
     cc = hipcc()
     pid = ".%d.tmp" % os.getpid()
-    todo = []
-    for name, (src, _, extra) in UNITS.items():
-        obj = os.path.join(OBJ, name + ".o")
-        flags = FLAGS + extra
-        if force or _stale(obj, unit_deps(name), flags):
-            todo.append((name, flags, [cc] + flags + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
-    relink = bool(todo) or not os.path.exists(OUT)
-    todo_vario = []
-    for name, (src, _) in UNITS_VARIO.items():
-        obj = os.path.join(OBJ, name + ".o")
-        if force or _stale(obj, vario_deps(name), FLAGS):
-            todo_vario.append((name, FLAGS, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
-    todo_vario3 = []
-    for name, (src, _) in UNITS_VARIO3.items():
-        obj = os.path.join(OBJ, name + ".o")
-        if force or _stale(obj, vario3_deps(name), FLAGS):
-            todo_vario3.append((name, FLAGS, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
-    todo_lik = []
-    for name, (src, _) in UNITS_LIK.items():
-        obj = os.path.join(OBJ, name + ".o")
-        if force or _stale(obj, lik_deps(name), FLAGS):
-            todo_lik.append((name, FLAGS, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
-    todo_grad = []
-    for name, (src, _) in UNITS_GRAD.items():
-        obj = os.path.join(OBJ, name + ".o")
-        if force or _stale(obj, grad_deps(name), FLAGS):
-            todo_grad.append((name, FLAGS, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
-    todo_vecchia = []
-    for name, (src, _) in UNITS_VECCHIA.items():
-        obj = os.path.join(OBJ, name + ".o")
-        if force or _stale(obj, vecchia_deps(name), FLAGS):
-            todo_vecchia.append((name, FLAGS, [cc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj + pid]))
+    todo, relink = [], []  # the compile jobs; the libraries to link
+    for lib in LIBRARIES:
+        before = len(todo)
+        for name, unit in lib.units.items():
+            obj = os.path.join(OBJ, name + ".o")
+            flags = FLAGS + (unit[2] if len(unit) > 2 else [])
+            if force or _stale(obj, lib.deps(name), flags):
+                todo.append((name, flags, [cc] + flags + ["-c", os.path.join(CSRC, unit[0]), "-o", obj + pid]))
+        if len(todo) > before or _stale(lib.out, lib.sources()):
+            relink.append(lib)
 
     def run(job):
         name, flags, cmd = job
@@ -234,29 +180,16 @@ def _build_locked(force, verbose, jobs):
             f.write(" ".join(flags))
         return name
 
-    todo.sort(key=lambda j: -COST.get(j[0].rstrip("0123456789"), 0))
+    todo.sort(key=lambda j: -COST.get(j[0].rstrip("0123456789"), 0))  # (stable: the units without a cost keep the table's order, last)
     with ThreadPoolExecutor(max_workers=jobs or min(len(UNITS), os.cpu_count() or 4)) as ex:
-        list(ex.map(run, todo + todo_vecchia + todo_vario + todo_vario3 + todo_lik + todo_grad))
-    # (-s: no static symbol table -- 90 kB; the C ABI and the kernels' host stubs are dynamic symbols, `nm -D` lists them)
-    links = []
-    if relink or _stale(OUT, all_sources()):
-        links.append((OUT, [os.path.join(OBJ, n + ".o") for n in UNITS], ["-ldl", "-Wl,-s"]))
-    if todo_vario or _stale(OUT_VARIO, [d for n in UNITS_VARIO for d in vario_deps(n)]):
-        links.append((OUT_VARIO, [os.path.join(OBJ, n + ".o") for n in UNITS_VARIO], ["-Wl,-s"]))
-    if todo_vario3 or _stale(OUT_VARIO3, [d for n in UNITS_VARIO3 for d in vario3_deps(n)]):
-        links.append((OUT_VARIO3, [os.path.join(OBJ, n + ".o") for n in UNITS_VARIO3], ["-Wl,-s"]))
-    if todo_lik or _stale(OUT_LIK, [d for n in UNITS_LIK for d in lik_deps(n)]):
-        links.append((OUT_LIK, [os.path.join(OBJ, n + ".o") for n in UNITS_LIK], ["-Wl,-s"]))
-    if todo_grad or _stale(OUT_GRAD, [d for n in UNITS_GRAD for d in grad_deps(n)]):
-        links.append((OUT_GRAD, [os.path.join(OBJ, n + ".o") for n in UNITS_GRAD], ["-Wl,-s"]))
-    if todo_vecchia or _stale(OUT_VECCHIA, [d for n in UNITS_VECCHIA for d in vecchia_deps(n)]):
-        links.append((OUT_VECCHIA, [os.path.join(OBJ, n + ".o") for n in UNITS_VECCHIA], ["-Wl,-s"]))
-    for out, objs, tail in links:
-        link = [cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out + pid] + tail
+        list(ex.map(run, todo))
+    for lib in relink:
+        objs = [os.path.join(OBJ, n + ".o") for n in lib.units]
+        link = [cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", lib.out + pid] + lib.tail
         if verbose:
             print(" ".join(link), flush=True)
         subprocess.run(link, check=True)
-        os.replace(out + pid, out)
+        os.replace(lib.out + pid, lib.out)
     return OUT
 
 

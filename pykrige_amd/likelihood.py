@@ -15,7 +15,7 @@ import os
 
 import numpy as np
 
-from . import core
+from . import _dl, core
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmiklik.so")
@@ -42,35 +42,9 @@ _lib = None
 def load():
     """dlopen libmiklik.so and declare the signatures.  Raises ImportError if it has not been built or is stale."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            "pykrige_amd: %s is missing -- build it with `python -m pykrige_amd.build` "
-            "(needs hipcc; there is no CPU fallback)" % LIB_PATH)
-    lib = C.CDLL(LIB_PATH)
-    have = getattr(lib, "mlk_abi_version", None)
-    version = None
-    if have is not None:
-        have.restype, have.argtypes = SIGNATURES["mlk_abi_version"]
-        version = have()
-    stale = "pykrige_amd: %s %%s, this package was written against ABI version %d -- rebuild it (`python -m pykrige_amd.build --force`)" % (
-        LIB_PATH, ABI_VERSION)
-    if version != ABI_VERSION:
-        raise ImportError(stale % ("has no mlk_abi_version" if version is None else "has ABI version %d" % version))
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % ("does not export %s" % name)) from None
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
-
-
-def _device():
-    return int(os.environ.get("MIK_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    if _lib is None:
+        _lib = _dl.open_library(LIB_PATH, "mlk", ABI_VERSION, SIGNATURES)
+    return _lib
 
 
 def _check_model(who, model):
@@ -84,22 +58,15 @@ def _check_model(who, model):
         raise ValueError("%s: variogram_model must be one of %s, got %r" % (who, ", ".join(repr(k) for k in MODEL_IDS), model))
 
 
-def gram(coords, model, parameters, W):
-    """``logdet, G = gram(coords, model, parameters, W)``: log det C and W^T C^-1 W on the GPU, one call of ``mlk_gram``.
-
-    coords: (N, 2) or (N, 3) anisotropy-adjusted Euclidean station coordinates, N >= 2.  model: 'gaussian', 'exponential', 'spherical' or
-    'hole-effect'.  parameters: the internal list [psill, range, nugget] (partial sill), psill > 0, range > 0, nugget >= 0.  W: (N,) or
-    (N, m) columns, 1 <= m <= 40.
-
-    C_ii = psill + nugget and, for i != j, C_ij = (psill + nugget) - gamma(d_ij) with the model formula of ``core.variogram_value`` in
-    float64 -- also at d = 0: two coincident distinct stations have C_ij = psill.  G is (m, m) and exactly symmetric.  Both results are
-    reproducible bit for bit from run to run, and an entry of G does not depend on where its two columns stand in W.  If C is not
-    positive definite in float64, logdet is ``inf`` and G is filled with NaN.  Argument errors raise ValueError before the library is
-    loaded; there is no CPU fallback."""
-    who = "gram"
+def _gram_arguments(who, coords, model, parameters, W, macro, plan_shape=None):
+    """The checks ``gram`` and ``VecchiaPlan.gram`` share -> n, ndim, psill, range, nugget, m and the transposed contiguous coordinates and
+    columns.  ``macro`` is the library's name for the column bound; with ``plan_shape`` the coordinates must have that (N, ndim)."""
     _check_model(who, model)
     X = np.asarray(coords, dtype=np.float64)
-    if X.ndim != 2 or X.shape[1] not in (2, 3):
+    if plan_shape is not None:
+        if X.shape != plan_shape:
+            raise ValueError("%s: coords must have the plan's shape (%d, %d), got %s" % ((who,) + plan_shape + (np.shape(coords),)))
+    elif X.ndim != 2 or X.shape[1] not in (2, 3):
         raise ValueError("%s: coords must have shape (N, 2) or (N, 3), got %s" % (who, np.shape(coords)))
     n, ndim = X.shape
     if n < 2:
@@ -114,28 +81,38 @@ def gram(coords, model, parameters, W):
     if Wa.ndim == 1:
         Wa = Wa[:, None]
     if Wa.ndim != 2 or Wa.shape[0] != n or not 1 <= Wa.shape[1] <= MAXCOLS:
-        raise ValueError("%s: W must have shape (N,) or (N, m) with N = %d stations and 1 <= m <= %d columns (MLK_MAXCOLS), got %s"
-                         % (who, n, MAXCOLS, np.shape(W)))
+        raise ValueError("%s: W must have shape (N,) or (N, m) with N = %d stations and 1 <= m <= %d columns (%s), got %s"
+                         % (who, n, MAXCOLS, macro, np.shape(W)))
     if not np.all(np.isfinite(X)):
         raise ValueError("%s: station coordinates must be finite" % who)
     if not np.all(np.isfinite(Wa)):
         raise ValueError("%s: W must be finite" % who)
-    m = int(Wa.shape[1])
-    ct = np.ascontiguousarray(X.T)
-    wt = np.ascontiguousarray(Wa.T)
+    return n, ndim, psill, rng, nugget, int(Wa.shape[1]), np.ascontiguousarray(X.T), np.ascontiguousarray(Wa.T)
+
+
+def gram(coords, model, parameters, W):
+    """``logdet, G = gram(coords, model, parameters, W)``: log det C and W^T C^-1 W on the GPU, one call of ``mlk_gram``.
+
+    coords: (N, 2) or (N, 3) anisotropy-adjusted Euclidean station coordinates, N >= 2.  model: 'gaussian', 'exponential', 'spherical' or
+    'hole-effect'.  parameters: the internal list [psill, range, nugget] (partial sill), psill > 0, range > 0, nugget >= 0.  W: (N,) or
+    (N, m) columns, 1 <= m <= 40.
+
+    C_ii = psill + nugget and, for i != j, C_ij = (psill + nugget) - gamma(d_ij) with the model formula of ``core.variogram_value`` in
+    float64 -- also at d = 0: two coincident distinct stations have C_ij = psill.  G is (m, m) and exactly symmetric.  Both results are
+    reproducible bit for bit from run to run, and an entry of G does not depend on where its two columns stand in W.  If C is not
+    positive definite in float64, logdet is ``inf`` and G is filled with NaN.  Argument errors raise ValueError before the library is
+    loaded; there is no CPU fallback."""
+    n, ndim, psill, rng, nugget, m, ct, wt = _gram_arguments("gram", coords, model, parameters, W, "MLK_MAXCOLS")
     G = np.zeros((m, m))
     logdet = C.c_double(0.0)
     info = C.c_int32(0)
     lib = load()
-    rc = lib.mlk_gram(_device(), n, ndim, ct.ctypes.data_as(_dp), MODEL_IDS[model], psill, rng, nugget, wt.ctypes.data_as(_dp), m,
+    rc = lib.mlk_gram(_dl.device(), n, ndim, ct.ctypes.data_as(_dp), MODEL_IDS[model], psill, rng, nugget, wt.ctypes.data_as(_dp), m,
                       C.byref(logdet), G.ctypes.data_as(_dp), C.byref(info))
     if rc == MLK_ENOTPD:
         return math.inf, np.full((m, m), np.nan)
     if rc != MLK_OK:
-        msg = (lib.mlk_last_error() or b"").decode("utf-8", "replace")
-        if rc == MLK_EINVAL:
-            raise ValueError(msg)
-        raise RuntimeError("libmiklik: %s (code %d)" % (msg, rc))
+        _dl.raise_for(lib, "mlk", "libmiklik", rc, MLK_EINVAL)
     return float(logdet.value), G
 
 
@@ -275,6 +252,38 @@ def _internal_parameters(who, model, variogram_parameters):
 _NLL_NAMES = ("variogram_model", "variogram_parameters")
 
 
+def _station_arguments(who, args, kwargs, names, accepted):
+    """The leading checks of the likelihoods and the fits -> raw coordinates, n, ndim, the fields (N, F), whether they came as (N, F),
+    the model and the named arguments.  ``names`` may be given by position after the values; ``accepted`` are the further keywords."""
+    raw, values, kw = _split(who, args, dict(kwargs), names)
+    unknown = set(kw) - set(names) - set(_ANIS2) - set(_ANIS3) - set(accepted)
+    if unknown:
+        raise TypeError("%s: unexpected argument %s" % (who, ", ".join(sorted(unknown))))
+    if "variogram_model" not in kw:
+        raise TypeError("%s: variogram_model is required" % who)
+    model = kw["variogram_model"]
+    _check_model(who, model)
+    n, ndim = raw.shape
+    if n < 2:
+        raise ValueError("%s: need at least two stations" % who)
+    if not np.all(np.isfinite(raw)):
+        raise ValueError("%s: station coordinates must be finite" % who)
+    v, many = _fields(who, values, n)
+    return raw, n, ndim, v, many, model, kw
+
+
+def _nll_arguments(who, args, kwargs, extra=()):
+    """The arguments of ``neg_log_likelihood`` and its kin, checked in their order -> raw coordinates, n, ndim, the fields, whether
+    they came as (N, F), the model, the internal parameters, the anisotropy scaling and angle, the adjusted coordinates, the trend
+    matrix X, reml and the named arguments (``extra``: the keywords accepted beside drift and reml)."""
+    raw, n, ndim, v, many, model, kw = _station_arguments(who, args, kwargs, _NLL_NAMES, ("drift", "reml") + tuple(extra))
+    par = _internal_parameters(who, model, kw.get("variogram_parameters"))
+    scaling, angle = _anisotropy(who, ndim, kw)
+    adj = _adjust(raw, scaling, angle)
+    X = _trend(who, kw.get("drift"), n, adj)
+    return raw, n, ndim, v, many, model, par, scaling, angle, adj, X, bool(kw.get("reml", True)), kw
+
+
 def neg_log_likelihood(x, y, *args, **kwargs):
     """The negative Gaussian log-likelihood of the stations under a variogram model, one Cholesky factorisation on the GPU.
 
@@ -296,26 +305,7 @@ def neg_log_likelihood(x, y, *args, **kwargs):
     A covariance matrix that is not positive definite in float64 gives ``inf``.  'linear' and 'power' (unbounded: no covariance exists)
     and non-finite input raise ValueError, a rank-deficient X raises ValueError, 'custom' raises NotImplementedError -- all before the
     library is loaded.  There is no CPU fallback."""
-    who = "neg_log_likelihood"
-    raw, values, kw = _split(who, (x, y) + args, dict(kwargs), _NLL_NAMES)
-    unknown = set(kw) - set(_NLL_NAMES) - set(_ANIS2) - set(_ANIS3) - {"drift", "reml"}
-    if unknown:
-        raise TypeError("%s: unexpected argument %s" % (who, ", ".join(sorted(unknown))))
-    if "variogram_model" not in kw:
-        raise TypeError("%s: variogram_model is required" % who)
-    model = kw["variogram_model"]
-    _check_model(who, model)
-    n, ndim = raw.shape
-    if n < 2:
-        raise ValueError("%s: need at least two stations" % who)
-    if not np.all(np.isfinite(raw)):
-        raise ValueError("%s: station coordinates must be finite" % who)
-    v, many = _fields(who, values, n)
-    par = _internal_parameters(who, model, kw.get("variogram_parameters"))
-    scaling, angle = _anisotropy(who, ndim, kw)
-    adj = _adjust(raw, scaling, angle)
-    X = _trend(who, kw.get("drift"), n, adj)
-    reml = bool(kw.get("reml", True))
+    raw, n, ndim, v, many, model, par, scaling, angle, adj, X, reml, kw = _nll_arguments("neg_log_likelihood", (x, y) + args, kwargs)
     logdet, G = gram(adj, model, par, np.hstack([v, X]))
     out = nll_from_gram(n, logdet, G, v.shape[1], reml, _pieces(X))
     return out if many else float(out[0])
@@ -381,125 +371,147 @@ def fit_variogram_ml(x, y, *args, **kwargs):
     from scipy.optimize import minimize
 
     who = "fit_variogram_ml"
-    raw, values, kw = _split(who, (x, y) + args, dict(kwargs), _FIT_NAMES)
-    unknown = set(kw) - set(_FIT_NAMES) - set(_ANIS2) - set(_ANIS3)
-    if unknown:
-        raise TypeError("%s: unexpected argument %s" % (who, ", ".join(sorted(unknown))))
-    if "variogram_model" not in kw:
-        raise TypeError("%s: variogram_model is required" % who)
-    model = kw["variogram_model"]
-    _check_model(who, model)
-    n, ndim = raw.shape
-    if n < 2:
-        raise ValueError("%s: need at least two stations" % who)
-    if not np.all(np.isfinite(raw)):
-        raise ValueError("%s: station coordinates must be finite" % who)
-    v, _ = _fields(who, values, n)
-    scaling0, angle0 = _anisotropy(who, ndim, kw)
-    drift = kw.get("drift")
-    X = _trend(who, drift, n, _adjust(raw, scaling0, angle0))
-    reml = bool(kw.get("reml", True))
-    fit_anis = bool(kw.get("fit_anisotropy", False))
-    method = kw.get("method", "nelder-mead")
+    fit = _Fit(who, (x, y) + args, kwargs, _FIT_NAMES)
+    method = fit.kw.get("method", "nelder-mead")
     if method is None:
         method = "nelder-mead"
     if not isinstance(method, str) or method.lower() not in FIT_METHODS:
         raise ValueError("%s: method must be one of %s, got %r" % (who, ", ".join(repr(k) for k in FIT_METHODS), method))
-    method = method.lower()
-    var = float(np.var(v))
-    if not var > 0.0:
-        raise ValueError("%s: the values are constant; there is no variogram to fit" % who)
-    diag = float(np.sqrt(np.sum((raw.max(axis=0) - raw.min(axis=0)) ** 2)))
-    if not diag > 0.0:
-        raise ValueError("%s: all stations coincide" % who)
-    floor = NUGGET_FLOOR * var
-    lim = {"psill": (1e-6 * var, 100.0 * var), "range": (1e-3 * diag, 10.0 * diag), "nugget": (0.0, 100.0 * var), "scaling": (0.05, 20.0)}
-    given = kw.get("bounds")
-    if given is not None:
-        if not isinstance(given, dict) or set(given) - set(lim):
-            raise ValueError("%s: bounds must be a dict with keys among 'psill', 'range', 'nugget', 'scaling'" % who)
-        for k, (lo, hi) in given.items():
-            lo, hi = float(lo), float(hi)
-            if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi and (lo > 0.0 or (k == "nugget" and lo >= 0.0))):
-                raise ValueError("%s: bounds[%r] must be (low, high) with 0 < low < high (nugget: 0 <= low)" % (who, k))
-            lim[k] = (lo, hi)
-    start = kw.get("start")
-    if start is None:
-        from . import variogram_fit
-
-        _, _, par0 = variogram_fit.fit(_adjust(raw, scaling0, angle0), v[:, 0], model, 6, False, "euclidean")
-        par0 = [float(t) for t in par0]
-    else:
-        par0 = _internal_parameters(who, model, start)
-    clip = lambda t, k: min(max(t, lim[k][0]), lim[k][1])
-    par0 = [clip(par0[0], "psill"), clip(par0[1], "range"), clip(par0[2], "nugget")]
-    pieces = _pieces(X)
-    moving = isinstance(drift, str) and fit_anis  # the trend columns are the adjusted coordinates: they move with the anisotropy
-    nscale = len(scaling0)
-
-    def unpack(t):
-        par = [math.exp(t[0]), math.exp(t[1]), max(math.exp(t[2]) - floor, 0.0)]
-        if fit_anis:
-            return par, [math.exp(s) for s in t[3:3 + nscale]], [float(a) for a in t[3 + nscale:]]
-        return par, scaling0, angle0
-
-    calls = [0]
-
-    def objective(t):
-        par, sc, an = unpack(t)
-        calls[0] += 1
-        adj = _adjust(raw, sc, an)
-        Xt = np.hstack([np.ones((n, 1)), adj]) if moving else X
-        logdet, G = gram(adj, model, par, np.hstack([v, Xt]))
-        return float(np.sum(nll_from_gram(n, logdet, G, v.shape[1], reml, _pieces(Xt) if moving else pieces)))
-
-    t0 = [math.log(par0[0]), math.log(par0[1]), math.log(par0[2] + floor)]
-    box = [tuple(math.log(b) for b in lim["psill"]), tuple(math.log(b) for b in lim["range"]),
-           (math.log(lim["nugget"][0] + floor), math.log(lim["nugget"][1] + floor))]
-    step = [0.4, 0.4, 0.6]
-    if fit_anis:
-        t0 += [math.log(clip(s, "scaling")) for s in scaling0] + list(angle0)
-        box += [tuple(math.log(b) for b in lim["scaling"])] * nscale + [(None, None)] * len(angle0)
-        step += [0.35] * nscale + [25.0] * len(angle0)
-    t0 = np.array(t0)
-    nll0 = objective(t0)  # the start is a candidate too: the result is never worse than it
-
-    def simplex(c, scale):
-        pts = [np.array(c)]
-        for k, s in enumerate(step):
-            q = np.array(c)
-            q[k] += s * scale if box[k][1] is None or q[k] + s * scale <= box[k][1] else -s * scale
-            pts.append(q)
-        return np.array(pts)
+    raw, n, ndim, v, model, reml = fit.raw, fit.n, fit.ndim, fit.v, fit.model, fit.reml
+    fit.prepare()
+    objective = fit.objective(lambda adj, par, W: gram(adj, model, par, W))
+    nll0 = objective(fit.t0)  # the start is a candidate too: the result is never worse than it
 
     def value_and_gradient(t):
         """The objective and its gradient in the search coordinates: one device call."""
-        par, sc, an = unpack(t)
-        calls[0] += 1
-        adj = _adjust(raw, sc, an)
-        Xt = np.hstack([np.ones((n, 1)), adj]) if moving else X
-        dco = anisotropy_derivatives(raw, sc, an) if fit_anis else np.zeros((0, n, ndim))
+        par, sc, an, adj, Xt, pieces = fit.trial(t)
+        dco = anisotropy_derivatives(raw, sc, an) if fit.fit_anis else np.zeros((0, n, ndim))
         logdet, G, grad, _ = gram_grad(adj, dco, model, par, v, Xt, reml)
-        f = float(np.sum(nll_from_gram(n, logdet, G, v.shape[1], reml, _pieces(Xt) if moving else pieces)))
+        f = float(np.sum(nll_from_gram(n, logdet, G, v.shape[1], reml, pieces)))
         g = np.sum(grad, axis=0)
         # d/dlog psill, d/dlog range, d/dlog(nugget + floor), d/dlog scaling; the angles are searched in degrees
-        chain = [par[0], par[1], par[2] + floor] + ([float(s_) for s_ in sc] + [1.0] * len(an) if fit_anis else [])
+        chain = [par[0], par[1], par[2] + fit.floor] + ([float(s_) for s_ in sc] + [1.0] * len(an) if fit.fit_anis else [])
         return f, g * np.array(chain)
 
-    best_t, best = t0, nll0
+    if method.lower() == "l-bfgs-b":
+        return _ml_fit(fit, *_fit_lbfgsb(minimize, objective, value_and_gradient, fit.t0, nll0, fit.box, fit.simplex))
+    return _ml_fit(fit, *_nelder_mead(minimize, objective, fit, nll0))
+
+
+class _Fit:
+    """What ``fit_variogram_ml`` and ``fit_variogram_vecchia`` share: the checked arguments (``__init__``), the search coordinates with
+    their start, bounds and simplex (``prepare``) and the objective over them.  The coordinates are t = [log psill, log range,
+    log(nugget + floor)], with fit_anisotropy followed by the log scalings and the angles in degrees."""
+
+    def __init__(self, who, args, kwargs, names, accepted=()):
+        self.who = who
+        self.raw, self.n, self.ndim, self.v, _, self.model, self.kw = _station_arguments(who, args, kwargs, names, accepted)
+        self.scaling0, self.angle0 = _anisotropy(who, self.ndim, self.kw)
+        self.adj0 = _adjust(self.raw, self.scaling0, self.angle0)
+        self.X = _trend(who, self.kw.get("drift"), self.n, self.adj0)
+        self.reml = bool(self.kw.get("reml", True))
+        self.fit_anis = bool(self.kw.get("fit_anisotropy", False))
+        self.calls = 0  # the device calls spent
+
+    def prepare(self, start_rows=None):
+        """The bounds, the start and the simplex steps.  With start=None the start is the constructor's least-squares fit of the binned
+        variogram of the first field, over all stations or over the rows ``start_rows()`` returns."""
+        who, raw, v = self.who, self.raw, self.v
+        var = float(np.var(v))
+        if not var > 0.0:
+            raise ValueError("%s: the values are constant; there is no variogram to fit" % who)
+        diag = float(np.sqrt(np.sum((raw.max(axis=0) - raw.min(axis=0)) ** 2)))
+        if not diag > 0.0:
+            raise ValueError("%s: all stations coincide" % who)
+        self.floor = floor = NUGGET_FLOOR * var
+        lim = {"psill": (1e-6 * var, 100.0 * var), "range": (1e-3 * diag, 10.0 * diag), "nugget": (0.0, 100.0 * var), "scaling": (0.05, 20.0)}
+        given = self.kw.get("bounds")
+        if given is not None:
+            if not isinstance(given, dict) or set(given) - set(lim):
+                raise ValueError("%s: bounds must be a dict with keys among 'psill', 'range', 'nugget', 'scaling'" % who)
+            for k, (lo, hi) in given.items():
+                lo, hi = float(lo), float(hi)
+                if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi and (lo > 0.0 or (k == "nugget" and lo >= 0.0))):
+                    raise ValueError("%s: bounds[%r] must be (low, high) with 0 < low < high (nugget: 0 <= low)" % (who, k))
+                lim[k] = (lo, hi)
+        start = self.kw.get("start")
+        if start is None:
+            from . import variogram_fit
+
+            rows = slice(None) if start_rows is None else start_rows()
+            par0 = [float(t) for t in variogram_fit.fit(self.adj0[rows], v[rows, 0], self.model, 6, False, "euclidean")[2]]
+        else:
+            par0 = _internal_parameters(who, self.model, start)
+        clip = lambda t, k: min(max(t, lim[k][0]), lim[k][1])
+        par0 = [clip(par0[0], "psill"), clip(par0[1], "range"), clip(par0[2], "nugget")]
+        self.pieces = _pieces(self.X)
+        # with drift='regional_linear' the trend columns are the adjusted coordinates: they move with the anisotropy
+        self.moving = isinstance(self.kw.get("drift"), str) and self.fit_anis
+        t0 = [math.log(par0[0]), math.log(par0[1]), math.log(par0[2] + floor)]
+        self.box = [tuple(math.log(b) for b in lim["psill"]), tuple(math.log(b) for b in lim["range"]),
+                    (math.log(lim["nugget"][0] + floor), math.log(lim["nugget"][1] + floor))]
+        self.step = [0.4, 0.4, 0.6]
+        if self.fit_anis:
+            nscale = len(self.scaling0)
+            t0 += [math.log(clip(s, "scaling")) for s in self.scaling0] + list(self.angle0)
+            self.box += [tuple(math.log(b) for b in lim["scaling"])] * nscale + [(None, None)] * len(self.angle0)
+            self.step += [0.35] * nscale + [25.0] * len(self.angle0)
+        self.t0 = np.array(t0)
+
+    def unpack(self, t):
+        """t -> the internal parameters [psill, range, nugget], the scaling list, the angle list."""
+        par = [math.exp(t[0]), math.exp(t[1]), max(math.exp(t[2]) - self.floor, 0.0)]
+        if self.fit_anis:
+            nscale = len(self.scaling0)
+            return par, [math.exp(s) for s in t[3:3 + nscale]], [float(a) for a in t[3 + nscale:]]
+        return par, self.scaling0, self.angle0
+
+    def trial(self, t):
+        """One evaluation at t is counted -> parameters, scaling, angle, adjusted coordinates, trend matrix, log det(X^T X)."""
+        par, sc, an = self.unpack(t)
+        self.calls += 1
+        adj = _adjust(self.raw, sc, an)
+        if self.moving:
+            Xt = np.hstack([np.ones((self.n, 1)), adj])
+            return par, sc, an, adj, Xt, _pieces(Xt)
+        return par, sc, an, adj, self.X, self.pieces
+
+    def objective(self, gram_of):
+        """The negative log-likelihood summed over the fields as a function of t; ``gram_of(adj, par, W)`` is the device call."""
+        def objective(t):
+            par, _, _, adj, Xt, pieces = self.trial(t)
+            logdet, G = gram_of(adj, par, np.hstack([self.v, Xt]))
+            return float(np.sum(nll_from_gram(self.n, logdet, G, self.v.shape[1], self.reml, pieces)))
+
+        return objective
+
+    def simplex(self, c, scale):
+        pts = [np.array(c)]
+        for k, s in enumerate(self.step):
+            q = np.array(c)
+            q[k] += s * scale if self.box[k][1] is None or q[k] + s * scale <= self.box[k][1] else -s * scale
+            pts.append(q)
+        return np.array(pts)
+
+
+def _nelder_mead(minimize, objective, fit, nll0):
+    """The derivative-free search from the start, and one restart from its result: (best t, best nll, converged, message)."""
+    best_t, best = fit.t0, nll0
     converged, message = False, ""
-    if method == "l-bfgs-b":
-        best_t, best, converged, message = _fit_lbfgsb(minimize, objective, value_and_gradient, t0, nll0, box, simplex)
-    for scale in (() if method == "l-bfgs-b" else (1.0, 0.5)):  # the search, and one restart from its result
-        res = minimize(objective, best_t, method="Nelder-Mead", bounds=box,
-                       options=dict(initial_simplex=simplex(best_t, scale), xatol=1e-3, fatol=1e-6, maxfev=200 * len(t0)))
+    for scale in (1.0, 0.5):
+        res = minimize(objective, best_t, method="Nelder-Mead", bounds=fit.box,
+                       options=dict(initial_simplex=fit.simplex(best_t, scale), xatol=1e-3, fatol=1e-6, maxfev=200 * len(fit.t0)))
         converged, message = converged or bool(res.success), str(res.message)
         if res.fun < best:
             best_t, best = np.array(res.x), float(res.fun)
-    par, sc, an = unpack(best_t)
-    names = _ANIS2 if ndim == 2 else _ANIS3
-    anis = dict(zip(names, list(sc) + list(an)))
-    return MLFit(model, [par[0] + par[2], par[1], par[2]], anis, best, calls[0], bool(converged and math.isfinite(best)), message, reml)
+    return best_t, best, converged, message
+
+
+def _ml_fit(fit, best_t, best, converged, message):
+    par, sc, an = fit.unpack(best_t)
+    anis = dict(zip(_ANIS2 if fit.ndim == 2 else _ANIS3, list(sc) + list(an)))
+    return MLFit(fit.model, [par[0] + par[2], par[1], par[2]], anis, best, fit.calls, bool(converged and math.isfinite(best)), message,
+                 fit.reml)
 
 
 # ------------------------------------------------------------------------------------------------------------- the analytic gradient
@@ -526,31 +538,9 @@ _lib_grad = None
 def load_grad():
     """dlopen libmikgrad.so and declare the signatures.  Raises ImportError if it has not been built or is stale."""
     global _lib_grad
-    if _lib_grad is not None:
-        return _lib_grad
-    if not os.path.exists(LIB_PATH_GRAD):
-        raise ImportError(
-            "pykrige_amd: %s is missing -- build it with `python -m pykrige_amd.build` "
-            "(needs hipcc; there is no CPU fallback)" % LIB_PATH_GRAD)
-    lib = C.CDLL(LIB_PATH_GRAD)
-    have = getattr(lib, "mlg_abi_version", None)
-    version = None
-    if have is not None:
-        have.restype, have.argtypes = SIGNATURES_GRAD["mlg_abi_version"]
-        version = have()
-    stale = "pykrige_amd: %s %%s, this package was written against ABI version %d -- rebuild it (`python -m pykrige_amd.build --force`)" % (
-        LIB_PATH_GRAD, ABI_VERSION_GRAD)
-    if version != ABI_VERSION_GRAD:
-        raise ImportError(stale % ("has no mlg_abi_version" if version is None else "has ABI version %d" % version))
-    for name, (res, args) in SIGNATURES_GRAD.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % ("does not export %s" % name)) from None
-        fn.restype = res
-        fn.argtypes = args
-    _lib_grad = lib
-    return lib
+    if _lib_grad is None:
+        _lib_grad = _dl.open_library(LIB_PATH_GRAD, "mlg", ABI_VERSION_GRAD, SIGNATURES_GRAD)
+    return _lib_grad
 
 
 def gram_grad(coords, dcoords, model, parameters, V, X, reml):
@@ -578,16 +568,13 @@ def gram_grad(coords, dcoords, model, parameters, V, X, reml):
     logdet = C.c_double(0.0)
     info = C.c_int32(0)
     lib = load_grad()
-    rc = lib.mlg_grad(_device(), n, ndim, ct.ctypes.data_as(_dp), ng, D.ctypes.data_as(_dp) if ng else None, MODEL_IDS[model], psill, rng,
+    rc = lib.mlg_grad(_dl.device(), n, ndim, ct.ctypes.data_as(_dp), ng, D.ctypes.data_as(_dp) if ng else None, MODEL_IDS[model], psill, rng,
                       nugget, vt.ctypes.data_as(_dp), F, xt.ctypes.data_as(_dp), p, 1 if reml else 0, C.byref(logdet), G.ctypes.data_as(_dp),
                       grad.ctypes.data_as(_dp), C.byref(info))
     if rc == MLG_ENOTPD:
         return math.inf, np.full((m, m), np.nan), np.full((F, 3 + ng), np.nan), int(info.value)
     if rc != MLG_OK:
-        msg = (lib.mlg_last_error() or b"").decode("utf-8", "replace")
-        if rc == MLG_EINVAL:
-            raise ValueError(msg)
-        raise RuntimeError("libmikgrad: %s (code %d)" % (msg, rc))
+        _dl.raise_for(lib, "mlg", "libmikgrad", rc, MLG_EINVAL)
     return float(logdet.value), G, grad, 0
 
 
@@ -641,26 +628,7 @@ def neg_log_likelihood_grad(x, y, *args, **kwargs):
 
     A covariance matrix that is not positive definite in float64 gives ``inf`` and a gradient of NaN.  The refusals are
     ``neg_log_likelihood``'s, raised before the library is loaded.  There is no CPU fallback."""
-    who = "neg_log_likelihood_grad"
-    raw, values, kw = _split(who, (x, y) + args, dict(kwargs), _NLL_NAMES)
-    unknown = set(kw) - set(_NLL_NAMES) - set(_ANIS2) - set(_ANIS3) - {"drift", "reml"}
-    if unknown:
-        raise TypeError("%s: unexpected argument %s" % (who, ", ".join(sorted(unknown))))
-    if "variogram_model" not in kw:
-        raise TypeError("%s: variogram_model is required" % who)
-    model = kw["variogram_model"]
-    _check_model(who, model)
-    n, ndim = raw.shape
-    if n < 2:
-        raise ValueError("%s: need at least two stations" % who)
-    if not np.all(np.isfinite(raw)):
-        raise ValueError("%s: station coordinates must be finite" % who)
-    v, many = _fields(who, values, n)
-    par = _internal_parameters(who, model, kw.get("variogram_parameters"))
-    scaling, angle = _anisotropy(who, ndim, kw)
-    adj = _adjust(raw, scaling, angle)
-    X = _trend(who, kw.get("drift"), n, adj)
-    reml = bool(kw.get("reml", True))
+    raw, n, ndim, v, many, model, par, scaling, angle, adj, X, reml, kw = _nll_arguments("neg_log_likelihood_grad", (x, y) + args, kwargs)
     logdet, G, grad, _ = gram_grad(adj, anisotropy_derivatives(raw, scaling, angle), model, par, v, X, reml)
     out = nll_from_gram(n, logdet, G, v.shape[1], reml, _pieces(X))
     return (out, grad) if many else (float(out[0]), grad[0])

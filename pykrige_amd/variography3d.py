@@ -14,6 +14,8 @@ import os
 
 import numpy as np
 
+from . import _dl
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmikvario3.so")
 
@@ -40,44 +42,14 @@ _lib = None
 def load():
     """dlopen libmikvario3.so and declare the signatures.  Raises ImportError if it has not been built or is stale."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            "pykrige_amd: %s is missing -- build it with `python -m pykrige_amd.build` "
-            "(needs hipcc; there is no CPU fallback)" % LIB_PATH)
-    lib = C.CDLL(LIB_PATH)
-    have = getattr(lib, "mkv3_abi_version", None)
-    version = None
-    if have is not None:
-        have.restype, have.argtypes = SIGNATURES["mkv3_abi_version"]
-        version = have()
-    stale = "pykrige_amd: %s %%s, this package was written against ABI version %d -- rebuild it (`python -m pykrige_amd.build --force`)" % (
-        LIB_PATH, ABI_VERSION)
-    if version != ABI_VERSION:
-        raise ImportError(stale % ("has no mkv3_abi_version" if version is None else "has ABI version %d" % version))
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % ("does not export %s" % name)) from None
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _dl.open_library(LIB_PATH, "mkv3", ABI_VERSION, SIGNATURES)
+    return _lib
 
 
 def _check(lib, rc):
-    if rc == MKV3_OK:
-        return
-    msg = (lib.mkv3_last_error() or b"").decode("utf-8", "replace")
-    if rc == MKV3_EINVAL:
-        raise ValueError(msg)
-    raise RuntimeError("libmikvario3: %s (code %d)" % (msg, rc))
-
-
-def _device():
-    return int(os.environ.get("MIK_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    if rc != MKV3_OK:
+        _dl.raise_for(lib, "mkv3", "libmikvario3", rc, MKV3_EINVAL)
 
 
 def direction_vectors(azimuths, dips):
@@ -235,7 +207,7 @@ def directional_variogram_3d(x, y, z, values, azimuths=None, dips=None, directio
     semi_sum = np.zeros((nf, na, nb))
     counts = np.zeros((na, nb), dtype=np.int64)
     lib = load()
-    _check(lib, lib.mkv3_directional(_device(), n, x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), z.ctypes.data_as(_dp),
+    _check(lib, lib.mkv3_directional(_dl.device(), n, x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), z.ctypes.data_as(_dp),
                                      v.ctypes.data_as(_dp), nf, u.ctypes.data_as(_dp), na, tol, bw, e.ctypes.data_as(_dp), nb,
                                      lag_sum.ctypes.data_as(_dp), semi_sum.ctypes.data_as(_dp), counts.ctypes.data_as(_ip)))
     semi = _mean(semi_sum, counts[None, :, :])
@@ -275,7 +247,7 @@ def variogram_map_3d(x, y, z, values, nx, ny, nz, dx, dy, dz):
     semi_sum = np.zeros((nf,) + shape)
     counts = np.zeros(shape, dtype=np.int64)
     lib = load()
-    _check(lib, lib.mkv3_map(_device(), n, x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), z.ctypes.data_as(_dp), v.ctypes.data_as(_dp), nf,
+    _check(lib, lib.mkv3_map(_dl.device(), n, x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), z.ctypes.data_as(_dp), v.ctypes.data_as(_dp), nf,
                              nx, ny, nz, dx, dy, dz, semi_sum.ctypes.data_as(_dp), counts.ctypes.data_as(_ip)))
     semi = _mean(semi_sum, counts[None])
     return (semi if many else semi[0]), counts

@@ -16,9 +16,9 @@ import os
 
 import numpy as np
 
-from .likelihood import (MODEL_IDS, MLFit, _adjust, _anisotropy, _check_model, _fields, _internal_parameters, _pieces, _split, _trend,
-                         nll_from_gram)
-from .likelihood import _ANIS2, _ANIS3, MAXCOLS, NUGGET_FLOOR
+from . import _dl
+from .likelihood import MODEL_IDS, _Fit, _gram_arguments, _ml_fit, _nelder_mead, _nll_arguments, _pieces, nll_from_gram
+from .likelihood import MLFit, _split, _trend  # noqa: F401 (the likelihood's own, importable from here as before)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmikvecchia.so")
@@ -48,42 +48,13 @@ _lib = None
 def load():
     """dlopen libmikvecchia.so and declare the signatures.  Raises ImportError if it has not been built or is stale."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            "pykrige_amd: %s is missing -- build it with `python -m pykrige_amd.build` "
-            "(needs hipcc; there is no CPU fallback)" % LIB_PATH)
-    lib = C.CDLL(LIB_PATH)
-    have = getattr(lib, "mvc_abi_version", None)
-    version = None
-    if have is not None:
-        have.restype, have.argtypes = SIGNATURES["mvc_abi_version"]
-        version = have()
-    stale = "pykrige_amd: %s %%s, this package was written against ABI version %d -- rebuild it (`python -m pykrige_amd.build --force`)" % (
-        LIB_PATH, ABI_VERSION)
-    if version != ABI_VERSION:
-        raise ImportError(stale % ("has no mvc_abi_version" if version is None else "has ABI version %d" % version))
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(stale % ("does not export %s" % name)) from None
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
-
-
-def _device():
-    return int(os.environ.get("MIK_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    if _lib is None:
+        _lib = _dl.open_library(LIB_PATH, "mvc", ABI_VERSION, SIGNATURES)
+    return _lib
 
 
 def _raise(lib, rc):
-    msg = (lib.mvc_last_error() or b"").decode("utf-8", "replace")
-    if rc == MVC_EINVAL:
-        raise ValueError(msg)
-    raise RuntimeError("libmikvecchia: %s (code %d)" % (msg, rc))
+    _dl.raise_for(lib, "mvc", "libmikvecchia", rc, MVC_EINVAL)
 
 
 def _check_m(who, m):
@@ -137,7 +108,7 @@ class VecchiaPlan:
         ct = np.ascontiguousarray(X.T)
         handle = _plan_p()
         lib = load()
-        rc = lib.mvc_plan_create(_device(), self.n, self.ndim, ct.ctypes.data_as(_dp), self.order.ctypes.data_as(_i32p), self.m,
+        rc = lib.mvc_plan_create(_dl.device(), self.n, self.ndim, ct.ctypes.data_as(_dp), self.order.ctypes.data_as(_i32p), self.m,
                                  C.byref(handle))
         if rc != MVC_OK:
             _raise(lib, rc)
@@ -164,30 +135,9 @@ class VecchiaPlan:
         depends only on its two columns.  coords may differ from the plan's -- a search that moves the anisotropy: the neighbour sets
         stay those of the plan's metric.  If a local system is not positive definite in float64, logdet is ``inf`` and G is NaN."""
         who = "VecchiaPlan.gram"
-        _check_model(who, model)
-        X = np.asarray(coords, dtype=np.float64)
-        if X.shape != (self.n, self.ndim):
-            raise ValueError("%s: coords must have the plan's shape (%d, %d), got %s" % (who, self.n, self.ndim, np.shape(coords)))
-        try:
-            psill, rng, nugget = (float(v) for v in parameters)
-        except (TypeError, ValueError):
-            raise ValueError("%s: parameters must be the three numbers [psill, range, nugget]" % who) from None
-        if not (math.isfinite(psill) and math.isfinite(rng) and math.isfinite(nugget) and psill > 0.0 and rng > 0.0 and nugget >= 0.0):
-            raise ValueError("%s: need finite psill > 0, range > 0 and nugget >= 0, got %r" % (who, [psill, rng, nugget]))
-        Wa = np.asarray(W, dtype=np.float64)
-        if Wa.ndim == 1:
-            Wa = Wa[:, None]
-        if Wa.ndim != 2 or Wa.shape[0] != self.n or not 1 <= Wa.shape[1] <= MAXCOLS:
-            raise ValueError("%s: W must have shape (N,) or (N, m) with N = %d stations and 1 <= m <= %d columns (MVC_MAXCOLS), got %s"
-                             % (who, self.n, MAXCOLS, np.shape(W)))
-        if not np.all(np.isfinite(X)):
-            raise ValueError("%s: station coordinates must be finite" % who)
-        if not np.all(np.isfinite(Wa)):
-            raise ValueError("%s: W must be finite" % who)
+        _, _, psill, rng, nugget, mc, ct, wt = _gram_arguments(who, coords, model, parameters, W, "MVC_MAXCOLS", (self.n, self.ndim))
         if self._handle is None:
             raise ValueError("%s: the plan is closed" % who)
-        mc = int(Wa.shape[1])
-        ct, wt = np.ascontiguousarray(X.T), np.ascontiguousarray(Wa.T)
         G = np.zeros((mc, mc))
         logdet, info = C.c_double(0.0), C.c_int32(0)
         lib = load()
@@ -235,7 +185,6 @@ def _check_plan(who, plan, n, ndim):
         raise ValueError("%s: the plan was built for (%d, %d) coordinates; these stations are (%d, %d)" % (who, plan.n, plan.ndim, n, ndim))
 
 
-_NLL_NAMES = ("variogram_model", "variogram_parameters")
 _PLAN_NAMES = ("m", "order", "seed")
 
 
@@ -254,25 +203,7 @@ def neg_log_likelihood_vecchia(x, y, *args, **kwargs):
     is not positive definite in float64 gives ``inf``.  Every refusal is raised before the library is loaded; there is no CPU
     fallback."""
     who = "neg_log_likelihood_vecchia"
-    raw, values, kw = _split(who, (x, y) + args, dict(kwargs), _NLL_NAMES)
-    unknown = set(kw) - set(_NLL_NAMES) - set(_ANIS2) - set(_ANIS3) - {"drift", "reml", "plan"} - set(_PLAN_NAMES)
-    if unknown:
-        raise TypeError("%s: unexpected argument %s" % (who, ", ".join(sorted(unknown))))
-    if "variogram_model" not in kw:
-        raise TypeError("%s: variogram_model is required" % who)
-    model = kw["variogram_model"]
-    _check_model(who, model)
-    n, ndim = raw.shape
-    if n < 2:
-        raise ValueError("%s: need at least two stations" % who)
-    if not np.all(np.isfinite(raw)):
-        raise ValueError("%s: station coordinates must be finite" % who)
-    v, many = _fields(who, values, n)
-    par = _internal_parameters(who, model, kw.get("variogram_parameters"))
-    scaling, angle = _anisotropy(who, ndim, kw)
-    adj = _adjust(raw, scaling, angle)
-    X = _trend(who, kw.get("drift"), n, adj)
-    reml = bool(kw.get("reml", True))
+    _, n, ndim, v, many, model, par, _, _, adj, X, reml, kw = _nll_arguments(who, (x, y) + args, kwargs, ("plan",) + _PLAN_NAMES)
     plan = kw.get("plan")
     if plan is not None:
         _check_plan(who, plan, n, ndim)
@@ -307,105 +238,12 @@ def fit_variogram_vecchia(x, y, *args, **kwargs):
     from scipy.optimize import minimize
 
     who = "fit_variogram_vecchia"
-    raw, values, kw = _split(who, (x, y) + args, dict(kwargs), _FIT_NAMES)
-    unknown = set(kw) - set(_FIT_NAMES) - set(_ANIS2) - set(_ANIS3) - set(_PLAN_NAMES)
-    if unknown:
-        raise TypeError("%s: unexpected argument %s" % (who, ", ".join(sorted(unknown))))
-    if "variogram_model" not in kw:
-        raise TypeError("%s: variogram_model is required" % who)
-    model = kw["variogram_model"]
-    _check_model(who, model)
-    n, ndim = raw.shape
-    if n < 2:
-        raise ValueError("%s: need at least two stations" % who)
-    if not np.all(np.isfinite(raw)):
-        raise ValueError("%s: station coordinates must be finite" % who)
-    v, _ = _fields(who, values, n)
-    scaling0, angle0 = _anisotropy(who, ndim, kw)
-    drift = kw.get("drift")
-    adj0 = _adjust(raw, scaling0, angle0)
-    X = _trend(who, drift, n, adj0)
-    reml = bool(kw.get("reml", True))
-    fit_anis = bool(kw.get("fit_anisotropy", False))
-    m, order, seed = _plan_arguments(who, kw)
-    order = _order(who, order, adj0, seed)
-    var = float(np.var(v))
-    if not var > 0.0:
-        raise ValueError("%s: the values are constant; there is no variogram to fit" % who)
-    diag = float(np.sqrt(np.sum((raw.max(axis=0) - raw.min(axis=0)) ** 2)))
-    if not diag > 0.0:
-        raise ValueError("%s: all stations coincide" % who)
-    floor = NUGGET_FLOOR * var
-    lim = {"psill": (1e-6 * var, 100.0 * var), "range": (1e-3 * diag, 10.0 * diag), "nugget": (0.0, 100.0 * var), "scaling": (0.05, 20.0)}
-    given = kw.get("bounds")
-    if given is not None:
-        if not isinstance(given, dict) or set(given) - set(lim):
-            raise ValueError("%s: bounds must be a dict with keys among 'psill', 'range', 'nugget', 'scaling'" % who)
-        for k, (lo, hi) in given.items():
-            lo, hi = float(lo), float(hi)
-            if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi and (lo > 0.0 or (k == "nugget" and lo >= 0.0))):
-                raise ValueError("%s: bounds[%r] must be (low, high) with 0 < low < high (nugget: 0 <= low)" % (who, k))
-            lim[k] = (lo, hi)
-    start = kw.get("start")
-    if start is None:
-        from . import variogram_fit
-
-        pick = np.sort(np.random.default_rng(seed).permutation(n)[:START_SUBSAMPLE])
-        _, _, par0 = variogram_fit.fit(adj0[pick], v[pick, 0], model, 6, False, "euclidean")
-        par0 = [float(t) for t in par0]
-    else:
-        par0 = _internal_parameters(who, model, start)
-    clip = lambda t, k: min(max(t, lim[k][0]), lim[k][1])
-    par0 = [clip(par0[0], "psill"), clip(par0[1], "range"), clip(par0[2], "nugget")]
-    pieces = _pieces(X)
-    moving = isinstance(drift, str) and fit_anis  # the trend columns are the adjusted coordinates: they move with the anisotropy
-    nscale = len(scaling0)
-
-    def unpack(t):
-        par = [math.exp(t[0]), math.exp(t[1]), max(math.exp(t[2]) - floor, 0.0)]
-        if fit_anis:
-            return par, [math.exp(s) for s in t[3:3 + nscale]], [float(a) for a in t[3 + nscale:]]
-        return par, scaling0, angle0
-
-    calls = [0]
-    with VecchiaPlan(adj0, m=m, order=order) as plan:
-
-        def objective(t):
-            par, sc, an = unpack(t)
-            calls[0] += 1
-            adj = _adjust(raw, sc, an)
-            Xt = np.hstack([np.ones((n, 1)), adj]) if moving else X
-            logdet, G = plan.gram(adj, model, par, np.hstack([v, Xt]))
-            return float(np.sum(nll_from_gram(n, logdet, G, v.shape[1], reml, _pieces(Xt) if moving else pieces)))
-
-        t0 = [math.log(par0[0]), math.log(par0[1]), math.log(par0[2] + floor)]
-        box = [tuple(math.log(b) for b in lim["psill"]), tuple(math.log(b) for b in lim["range"]),
-               (math.log(lim["nugget"][0] + floor), math.log(lim["nugget"][1] + floor))]
-        step = [0.4, 0.4, 0.6]
-        if fit_anis:
-            t0 += [math.log(clip(s, "scaling")) for s in scaling0] + list(angle0)
-            box += [tuple(math.log(b) for b in lim["scaling"])] * nscale + [(None, None)] * len(angle0)
-            step += [0.35] * nscale + [25.0] * len(angle0)
-        t0 = np.array(t0)
-        nll0 = objective(t0)  # the start is a candidate too: the result is never worse than it
-
-        def simplex(c, scale):
-            pts = [np.array(c)]
-            for k, s in enumerate(step):
-                q = np.array(c)
-                q[k] += s * scale if box[k][1] is None or q[k] + s * scale <= box[k][1] else -s * scale
-                pts.append(q)
-            return np.array(pts)
-
-        best_t, best = t0, nll0
-        converged, message = False, ""
-        for scale in (1.0, 0.5):  # the search, and one restart from its result
-            res = minimize(objective, best_t, method="Nelder-Mead", bounds=box,
-                           options=dict(initial_simplex=simplex(best_t, scale), xatol=1e-3, fatol=1e-6, maxfev=200 * len(t0)))
-            converged, message = converged or bool(res.success), str(res.message)
-            if res.fun < best:
-                best_t, best = np.array(res.x), float(res.fun)
-    par, sc, an = unpack(best_t)
-    names = _ANIS2 if ndim == 2 else _ANIS3
-    anis = dict(zip(names, list(sc) + list(an)))
-    return MLFit(model, [par[0] + par[2], par[1], par[2]], anis, best, calls[0], bool(converged and math.isfinite(best)), message, reml)
+    fit = _Fit(who, (x, y) + args, kwargs, _FIT_NAMES, _PLAN_NAMES)
+    m, order, seed = _plan_arguments(who, fit.kw)
+    order = _order(who, order, fit.adj0, seed)
+    fit.prepare(lambda: np.sort(np.random.default_rng(seed).permutation(fit.n)[:START_SUBSAMPLE]))
+    with VecchiaPlan(fit.adj0, m=m, order=order) as plan:
+        objective = fit.objective(lambda adj, par, W: plan.gram(adj, fit.model, par, W))
+        nll0 = objective(fit.t0)  # the start is a candidate too: the result is never worse than it
+        result = _nelder_mead(minimize, objective, fit, nll0)
+    return _ml_fit(fit, *result)
