@@ -121,7 +121,21 @@ def _stale(target, deps, flags=None):
 
 
 def up_to_date():
-    return not any(_stale(lib.out, lib.sources()) for lib in LIBRARIES)
+    """Every library is newer than its sources, and no object's recorded command line differs from this checkout's -- a tree that was
+    moved or copied after it was built records another include path.  (The compression flags aside: a hipcc without them records their
+    absence.  An object without a stamp -- the build directory was not shipped -- is taken on its library's age.)"""
+    plain = lambda flags: [c for c in flags if c not in COMPRESS]
+    for lib in LIBRARIES:
+        if _stale(lib.out, lib.sources()):
+            return False
+        for name, unit in lib.units.items():
+            try:
+                stamp = open(os.path.join(OBJ, name + ".flags")).read().split()
+            except OSError:
+                continue
+            if plain(stamp) != plain(FLAGS + (unit[2] if len(unit) > 2 else [])):
+                return False
+    return True
 
 
 def build_library(force=False, verbose=False, jobs=None):

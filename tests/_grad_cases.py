@@ -39,7 +39,16 @@ CASES = {
     "n129_exp3d_f32_p8": dict(n=129, ndim=3, model="exponential", par=[1.0, 0.5, 0.1], F=32, p=8, reml=True, **A3),
     "n200_hole_f1": dict(n=200, ndim=2, model="hole-effect", par=[1.0, 0.1, 0.1], F=1, p=1, reml=True, **A2),  # the short range
     "n333_sph_f7_p4": dict(n=333, ndim=2, model="spherical", par=[1.0, 0.4, 0.05], F=7, p=4, reml=True, **A2),  # exact zeros
+    # whole 64 x 64 pair tiles and one row past them: N = 128 (two tiles a side), 192 | 193, 256 | 257, with F = 1 | 8 | 9 around the
+    # eight-field chunk.  The reference inverts C in long double, so 257 is the last.  psill 1, nugget 0.1: kappa_2 <= 1.1 N / 0.1
+    "n128_exp_f8": dict(n=128, ndim=2, model="exponential", par=[1.0, 0.5, 0.1], F=8, p=1, reml=True, **A2),
+    "n192_gau3d_f9_ml": dict(n=192, ndim=3, model="gaussian", par=[1.0, 0.2, 0.1], F=9, p=2, reml=False, **A3),
+    "n193_sph_f1_p3": dict(n=193, ndim=2, model="spherical", par=[1.0, 0.4, 0.1], F=1, p=3, reml=True, **A2),
+    "n256_hole_f9": dict(n=256, ndim=2, model="hole-effect", par=[1.0, 0.05, 0.1], F=9, p=1, reml=True, **A2),  # (range 0.05: see _lik_cases)
+    "n257_exp3d_f8_p4": dict(n=257, ndim=3, model="exponential", par=[1.0, 0.5, 0.1], F=8, p=4, reml=True, **A3),
 }
+# the cases above that close the gaps between the tile edges: their worst err / bar is what profiles/fit_edges_parity.txt records
+EDGES = ("n128_exp_f8", "n192_gau3d_f9_ml", "n193_sph_f1_p3", "n256_hole_f9", "n257_exp3d_f8_p4")
 # the small problems on which central differences of the long-double objective check the reference itself (CPU only)
 HOST_CASES = {
     "h_exp2d_ml": dict(n=40, ndim=2, model="exponential", par=[1.0, 0.5, 0.1], F=2, p=1, reml=False, **A2),

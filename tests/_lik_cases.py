@@ -16,6 +16,7 @@ trailing matrix is C_kj - 1 * C_j0 = 0 exactly, it stays zero through every late
 of column k is 0 -- in any blocking, in float64 and in long double alike.  The failing column is k + 1, counted from 1.
 """
 import functools
+import os
 
 import numpy as np
 
@@ -43,7 +44,19 @@ CASES = {
     "n200_exp_m1": dict(n=200, ndim=2, model="exponential", par=[1.0, 0.5, 0.1], m=1),
     "n333_sph_m7": dict(n=333, ndim=2, model="spherical", par=[1.0, 0.4, 0.05], m=7),  # range < domain: exact zeros in C
     "n700_exp_m17": dict(n=700, ndim=2, model="exponential", par=[1.0, 1.0, 0.01], m=17),
+    # a whole number of tiles, and one row past it: N = 128 (one update tile, two block columns), 192 (three block columns), 256 | 257,
+    # 512 | 513; m = 24 | 25 and 32 | 33 straddle the eight-column groups and the 16-row padding of W^T.  psill 1, nugget 0.1: by
+    # Gershgorin kappa_2 <= 1.1 N / 0.1 for the three valid models; hole-effect at N = 256 needs range 0.05 to stay positive definite in
+    # the plane (at range 0.1 the pivot of column 114 fails) and has kappa_2 = 8.4
+    "n128_gau_m24": dict(n=128, ndim=2, model="gaussian", par=[1.0, 0.2, 0.1], m=24),
+    "n192_sph3d_m25": dict(n=192, ndim=3, model="spherical", par=[1.0, 0.4, 0.1], m=25),
+    "n256_hole_m32": dict(n=256, ndim=2, model="hole-effect", par=[1.0, 0.05, 0.1], m=32),
+    "n257_exp3d_m33": dict(n=257, ndim=3, model="exponential", par=[1.0, 0.5, 0.1], m=33),
+    "n512_sph_m1": dict(n=512, ndim=2, model="spherical", par=[1.0, 0.4, 0.1], m=1),
+    "n513_gau3d_m7": dict(n=513, ndim=3, model="gaussian", par=[1.0, 0.2, 0.1], m=7),
 }
+# the cases above that close the gaps between the tile edges: their worst err / bar is what profiles/fit_edges_parity.txt records
+EDGES = ("n128_gau_m24", "n192_sph3d_m25", "n256_hole_m32", "n257_exp3d_m33", "n512_sph_m1", "n513_gau3d_m7")
 # not positive definite -- two coincident stations with zero nugget, and the hole-effect model: name -> case, and the 1-based column of the
 # pivot that fails
 NOT_PD = {
@@ -52,6 +65,16 @@ NOT_PD = {
     # hole-effect at range 0.5: the leading 18 x 18 block has an eigenvalue of -0.05, the 17 x 17 one of +0.02 -- far from rounding
     "notpd_hole_n127": (dict(n=127, ndim=2, model="hole-effect", par=[1.0, 0.5, 0.1], m=1), 18),
 }
+
+
+def record(line):
+    """Print a figure, and append it to the file the environment variable FIT_EDGES_PARITY_OUT names (never by default): how
+    profiles/fit_edges_parity.txt is written."""
+    print(line)
+    path = os.environ.get("FIT_EDGES_PARITY_OUT")
+    if path:
+        with open(path, "a") as f:
+            f.write(line + "\n")
 
 
 def inputs(case):

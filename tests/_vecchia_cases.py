@@ -28,10 +28,41 @@ DEVICE = [("n2_exp_m1", 1), ("n63_sph3d_m7", 64), ("n64_exp_m16", 15), ("n64_exp
 # (lambda_max <= N * 1.1) and the nugget (lambda_min >= 0.1); the bar uses the computed kappa_2
 BIG = dict(n=3000, ndim=2, model="exponential", par=[1.0, 0.5, 0.1], m=1)
 BIG_M = 10
+# Cases of this module alone (the dense reference of _lik_cases would not finish at these N), in that module's form; `m` is the number of
+# W columns.  psill 1, nugget 0.1: kappa_2 <= 1.1 N / 0.1 <= 2.3e4 by Gershgorin; the bar uses the computed kappa_2.
+#   v1023 .. v2049: k_vec_reduce sums RB = 1024 positions per partial -- one partial short of full, full, a second partial of one
+#   position, two full partials, a third of one position; v1025_exp_c17: the same edge with the widest local systems and 8 + 8 + 1 columns.
+#   w*: k_vec_solve packs SOLVE_WAVES * (64 / KPAD) = 4 * 64 / KPAD stations into a workgroup and mvc_plan_gram picks KPAD = 16 for
+#   m <= 16, 32 for m <= 32 and 64 beyond (mik_vecchia.hip): 16, 8 and 4 stations.  N one below, at and one above each count, 9 columns.
+EDGE = {
+    "v1023_exp": dict(n=1023, ndim=2, model="exponential", par=[1.0, 0.5, 0.1], m=1),
+    "v1024_sph3d": dict(n=1024, ndim=3, model="spherical", par=[1.0, 0.4, 0.1], m=1),
+    "v1025_gau": dict(n=1025, ndim=2, model="gaussian", par=[1.0, 0.2, 0.1], m=1),
+    "v2048_exp3d": dict(n=2048, ndim=3, model="exponential", par=[1.0, 0.5, 0.1], m=1),
+    "v2049_sph": dict(n=2049, ndim=2, model="spherical", par=[1.0, 0.4, 0.1], m=1),
+    "v1025_exp_c17": dict(n=1025, ndim=2, model="exponential", par=[1.0, 0.5, 0.1], m=17),
+    "w15_exp": dict(n=15, ndim=2, model="exponential", par=[1.0, 0.5, 0.1], m=9),
+    "w16_gau3d": dict(n=16, ndim=3, model="gaussian", par=[1.0, 0.2, 0.1], m=9),
+    "w17_sph": dict(n=17, ndim=2, model="spherical", par=[1.0, 0.4, 0.1], m=9),
+    "w7_exp3d": dict(n=7, ndim=3, model="exponential", par=[1.0, 0.5, 0.1], m=9),
+    "w8_sph": dict(n=8, ndim=2, model="spherical", par=[1.0, 0.4, 0.1], m=9),
+    "w9_gau": dict(n=9, ndim=2, model="gaussian", par=[1.0, 0.2, 0.1], m=9),
+    "w3_exp": dict(n=3, ndim=2, model="exponential", par=[1.0, 0.5, 0.1], m=9),
+    "w4_gau": dict(n=4, ndim=2, model="gaussian", par=[1.0, 0.2, 0.1], m=9),
+    "w5_sph3d": dict(n=5, ndim=3, model="spherical", par=[1.0, 0.4, 0.1], m=9),
+}
+# (case, m) of the edges above, and of the dense edge cases of _lik_cases with 24 | 25 | 32 | 33 columns
+EDGE_DEVICE = [("v1023_exp", 3), ("v1024_sph3d", 3), ("v1025_gau", 3), ("v2048_exp3d", 3), ("v2049_sph", 3), ("v1025_exp_c17", 64),
+               ("w15_exp", 16), ("w16_gau3d", 16), ("w17_sph", 16), ("w7_exp3d", 32), ("w8_sph", 32), ("w9_gau", 32), ("w3_exp", 64),
+               ("w4_gau", 64), ("w5_sph3d", 64), ("n128_gau_m24", 10), ("n192_sph3d_m25", 20), ("n256_hole_m32", 16), ("n257_exp3d_m33", 33)]
+DEVICE = DEVICE + EDGE_DEVICE
+# k_vec_knn stages candidates through LDS in tiles of TC = 256: a last tile that is one short of full, full, or holds one candidate
+KNN_EDGE_SIZES = (255, 256, 257, 512, 513)
+KNN_EDGE_M = (1, 16, 33, 64)
 
 
 def case_of(name):
-    return BIG if name == "big" else lc.CASES[name]
+    return BIG if name == "big" else EDGE[name] if name in EDGE else lc.CASES[name]
 
 
 def neighbours_ref(X, order, m):

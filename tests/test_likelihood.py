@@ -3,8 +3,9 @@
 The bar (derived there): every entry of G within N 2^-52 kappa_2(C) of the reference relative to sqrt(G_aa G_bb), logdet within the same
 number absolutely.  The shapes are the smallest at which the blocking of mik_k_lik.h can go wrong -- N = 2, 63, 64, 65, 127, 129 around
 the 64-column block and the 128-row update tile, N = 200, 333, 700 with several block columns and update tiles, m = 1, 7, 16, 17, 40 around
-the 16-row padding of W^T -- in 2-D and 3-D, each model, one coincident pair with a nugget, and three inputs that are not positive
-definite.  Every figure is printed before it is asserted; profiles/likelihood_parity.txt holds them."""
+the 16-row padding of W^T, and the whole tiles N = 128, 192, 256 | 257, 512 | 513 with m = 24 | 25, 32 | 33 -- in 2-D and 3-D, each model,
+one coincident pair with a nugget, and three inputs that are not positive definite.  Every figure is printed before it is asserted;
+profiles/likelihood_parity.txt and profiles/fit_edges_parity.txt hold them."""
 import ctypes
 import functools
 import math
@@ -35,8 +36,8 @@ def test_gram_is_within_the_bar_symmetric_and_reproducible(name):
     ref_logdet, ref_G, kappa, bar = lc.reference(name)
     logdet, G = device(name)
     el, eg = lc.errors(logdet, G, ref_logdet, ref_G)
-    print("%-16s N %4d m %2d kappa_2 %9.3g bar %9.3g logdet error %9.3g G error %9.3g worst/bar %8.3g"
-          % (name, case["n"], case["m"], kappa, bar, el, eg, max(el, eg) / bar))
+    (lc.record if name in lc.EDGES else print)("gram      %-16s N %4d m %2d kappa_2 %9.3g bar %9.3g logdet error %9.3g G error %9.3g worst/bar %8.3g"
+                                               % (name, case["n"], case["m"], kappa, bar, el, eg, max(el, eg) / bar))
     assert G.shape == (case["m"], case["m"]) and np.array_equal(G, G.T)
     assert el <= bar and eg <= bar, (name, el, eg, bar)
     X, W = lc.inputs(case)
@@ -76,6 +77,25 @@ def test_a_matrix_that_is_not_positive_definite_is_answered_and_harms_nothing(na
     Xg, Wg = lc.inputs(lc.CASES[good])
     again = lk.gram(Xg, lc.CASES[good]["model"], lc.CASES[good]["par"], Wg)
     assert again[0] == first[0] and np.array_equal(again[1], first[1])
+
+
+def test_forty_one_columns_are_refused_and_harm_nothing():
+    """MLK_MAXCOLS = 40 is a case; 41 is refused by ``gram`` with a ValueError, and the valid call that follows returns the bits it
+    returned before."""
+    good = "n129_exp3d_m40"
+    case = lc.CASES[good]
+    X, W = lc.inputs(case)
+    first = device(good)
+    with pytest.raises(ValueError, match="MLK_MAXCOLS"):
+        lk.gram(X, case["model"], case["par"], np.hstack([W, W[:, :1]]))
+    lib = lk.load()  # the library's own refusal, past the Python check
+    ct, wt = np.ascontiguousarray(X.T), np.ascontiguousarray(np.hstack([W, W[:, :1]]).T)
+    out, ld, info = np.full((41, 41), 7.0), ctypes.c_double(7.0), ctypes.c_int32(-5)
+    rc = lib.mlk_gram(0, case["n"], case["ndim"], ct.ctypes.data_as(lk._dp), lk.MODEL_IDS[case["model"]], *case["par"],
+                      wt.ctypes.data_as(lk._dp), 41, ctypes.byref(ld), out.ctypes.data_as(lk._dp), ctypes.byref(info))
+    assert rc == lk.MLK_EINVAL and b"MLK_MAXCOLS" in lib.mlk_last_error() and ld.value == 7.0 and np.all(out == 7.0)
+    again = lk.gram(X, case["model"], case["par"], W)
+    assert again[0] == first[0] and np.array_equal(again[1].view(np.int64), first[1].view(np.int64))
 
 
 # ------------------------------------------------------------------------------------------------------------- the likelihood

@@ -3,7 +3,8 @@ tests/_grad_cases.py.
 
 The bar (derived there): entry (f, k) of the gradient within N 2^-52 kappa_2(C) (1/2 |P|_F |D_k|_F + |a_f|^2 |D_k|_F) of the reference.
 The cases sit at the edges of the 64-column blocks (N = 2, 63, 64, 65, 129), of the rule that identity row i joins the elimination at
-block column i / 64 (N = 129, 200, 333: two to six block columns) and of the eight-field chunks (F = 1, 7, 8, 9, 32), in 2-D and 3-D,
+block column i / 64 (N = 129, 200, 333: two to six block columns), of the 64 x 64 pair tiles of k_grad_pairs (N = 128, 192 | 193,
+256 | 257) and of the eight-field chunks (F = 1, 7, 8, 9, 32), in 2-D and 3-D,
 each model, ML and REML, one coincident pair with a nugget, exact zeros beyond a spherical range, and the three inputs of
 tests/_lik_cases.py that are not positive definite.  logdet, G and nll are held to ``gram`` / ``neg_log_likelihood`` bit for bit.
 Every figure is printed before it is asserted; profiles/likelihood_grad_parity.txt holds them."""
@@ -43,9 +44,9 @@ def test_the_gradient_is_within_its_bar_and_the_pieces_are_grams_bit_for_bit(nam
     ng = 2 if case["ndim"] == 2 else 5
     assert info == 0 and grad.shape == (case["F"], 3 + ng) and np.all(np.isfinite(grad))
     frac = np.abs(grad.astype(gc.LD) - ref) / bar
-    print("%-18s N %3d F %2d p %d %s kappa_2 %8.3g  worst / bar per parameter: %s  max |grad| %.3g"
-          % (name, case["n"], case["F"], X.shape[1], "REML" if case["reml"] else "ML  ", kappa,
-             " ".join("%8.2e" % float(t) for t in frac.max(axis=0)), float(np.abs(grad).max())))
+    (lc.record if name in gc.EDGES else print)("gram_grad %-18s N %3d F %2d p %d %s kappa_2 %8.3g  worst / bar per parameter: %s  max |grad| %.3g  worst/bar %8.3g"
+                                               % (name, case["n"], case["F"], X.shape[1], "REML" if case["reml"] else "ML  ", kappa,
+                                                  " ".join("%8.2e" % float(t) for t in frac.max(axis=0)), float(np.abs(grad).max()), float(frac.max())))
     assert np.all(frac <= 1.0), (name, float(frac.max()))
     # logdet and G are mlk_gram's bits
     logdet4, G4 = lk.gram(adj, case["model"], case["par"], np.hstack([V, X]))
@@ -69,6 +70,21 @@ def test_fewer_geometry_parameters_leave_the_others_alone():
     for keep in (0, 1):
         got = lk.gram_grad(adj, dco[:keep], case["model"], case["par"], V, X, case["reml"])
         assert got[2].shape == (case["F"], 3 + keep) and np.array_equal(bits(got[2]), bits(grad[:, :3 + keep]))
+
+
+def test_forty_one_columns_are_refused_and_harm_nothing():
+    """F + p = 40 is a case (n129_exp3d_f32_p8); F + p = 41 is refused by ``gram_grad`` with a ValueError on either side -- 33 fields, or
+    9 trend columns -- and the valid call that follows returns the bits it returned before."""
+    good = "n129_exp3d_f32_p8"
+    case = gc.CASES[good]
+    adj, dco, V, X = gc.problem(case)
+    first = device(good)
+    with pytest.raises(ValueError, match="MLG_MAXFIELDS"):
+        lk.gram_grad(adj, dco, case["model"], case["par"], np.hstack([V, V[:, :1]]), X, case["reml"])
+    with pytest.raises(ValueError, match="MLG_MAXTREND"):
+        lk.gram_grad(adj, dco, case["model"], case["par"], V, np.hstack([X, V[:, :1]]), case["reml"])
+    again = lk.gram_grad(adj, dco, case["model"], case["par"], V, X, case["reml"])
+    assert again[0] == first[0] and np.array_equal(bits(again[1]), bits(first[1])) and np.array_equal(bits(again[2]), bits(first[2]))
 
 
 def _problem(n, ndim, seed, nf=1):

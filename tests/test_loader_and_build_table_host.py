@@ -127,3 +127,21 @@ def test_the_libraries_table_is_behind_every_public_name_of_the_build():
     assert build.all_sources() == libs[0].sources() and len(build.all_sources()) == len(set(build.all_sources()))
     assert set(build.all_sources()) == {d for name in build.UNITS for d in build.unit_deps(name)}
     assert all(lib.sources() == lib.deps(next(iter(lib.units))) for lib in libs[1:])
+
+
+def test_a_tree_built_under_another_path_is_not_up_to_date(monkeypatch):
+    """The command line of every object is kept beside it; a checkout that was moved or copied after its build records another include
+    path, and ``up_to_date`` must say so, so that ``build_library`` recompiles instead of handing out objects of another command line.
+    The compression flags are no difference (a hipcc without them records their absence), nor is an object without a stamp."""
+    build.build_library()
+    assert build.up_to_date()
+    moved = [c if not c.startswith("-I") else "-I" + os.path.join(os.sep, "elsewhere", "include") for c in build.FLAGS]
+    monkeypatch.setattr(build, "FLAGS", moved)
+    assert not build.up_to_date()
+    monkeypatch.undo()
+    assert build.up_to_date()
+    monkeypatch.setattr(build, "FLAGS", [c for c in build.FLAGS if c not in build.COMPRESS])
+    assert build.up_to_date()
+    monkeypatch.undo()
+    monkeypatch.setattr(build, "OBJ", os.path.join(build.OBJ, "no_such_directory"))
+    assert build.up_to_date()

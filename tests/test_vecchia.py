@@ -1,8 +1,9 @@
 """vecchia.VecchiaPlan / neg_log_likelihood_vecchia / fit_variogram_vecchia on the GPU against tests/_vecchia_cases.py: the neighbour sets
 equal the NumPy restatement exactly, and log det and W^T C^-1 W are held to the long-double brute force within the project's bar --
 N 2^-52 kappa_2(C) relative to sqrt(G_aa G_bb) for G, the same number absolutely for logdet, C the full covariance of the case.  The shapes
-straddle the size classes of k_vec_solve (m = 15 | 16 | 17, 32 | 33, 64), the 64-position blocks of k_vec_knn and the 1024-position
-blocks of k_vec_reduce.  Every figure is printed before it is asserted and appended to profiles/vecchia_parity.txt when the environment
+straddle the size classes of k_vec_solve (m = 15 | 16 | 17, 32 | 33, 64) and the stations one of its workgroups takes in each class
+(N = 15 | 16 | 17, 7 | 8 | 9, 3 | 4 | 5), the 64-position blocks and 256-candidate tiles of k_vec_knn (N = 255 | 256 | 257, 512 | 513) and the
+1024-position blocks of k_vec_reduce (N = 1023 | 1024 | 1025, 2048 | 2049).  Every figure is printed before it is asserted and appended to profiles/vecchia_parity.txt when the environment
 variable VECCHIA_PARITY_OUT names a file."""
 import ctypes
 import math
@@ -22,12 +23,13 @@ pytestmark = pytest.mark.gpu
 LD = np.longdouble
 
 
-def record(line):
+def record(line, edge=False):
+    """``edge``: a case of ``_vecchia_cases.EDGE_DEVICE``, also appended to the file FIT_EDGES_PARITY_OUT names."""
     print(line)
-    path = os.environ.get("VECCHIA_PARITY_OUT")
-    if path:
-        with open(path, "a") as f:
-            f.write(line + "\n")
+    for path in (os.environ.get("VECCHIA_PARITY_OUT"), os.environ.get("FIT_EDGES_PARITY_OUT") if edge else None):
+        if path:
+            with open(path, "a") as f:
+                f.write(line + "\n")
 
 
 # ------------------------------------------------------------------------------------------------------------- neighbour sets
@@ -45,6 +47,38 @@ def test_the_neighbour_sets_are_the_reference_exactly(n, ndim):
             got = plan.neighbours
         assert got.shape == (n, m) and got.dtype == np.int32
         assert np.array_equal(got, vcs.neighbours_ref(X, plan.order, m)), (n, ndim, m)
+
+
+@pytest.mark.parametrize("ndim", [2, 3])
+@pytest.mark.parametrize("n", vcs.KNN_EDGE_SIZES)
+def test_the_neighbour_sets_at_the_edges_of_the_candidate_tile_are_the_reference_exactly(n, ndim):
+    """k_vec_knn stages TC = 256 candidates at a time: N = 255 | 256 | 257 and 512 | 513 end on a tile that is one short of full, full,
+    or holds a single candidate; m = 1, 16, 33, 64."""
+    X = _stations(n, ndim)
+    for m in vcs.KNN_EDGE_M:
+        with vc.VecchiaPlan(X, m=m) as plan:
+            got = plan.neighbours
+        assert got.shape == (n, m) and np.array_equal(got, vcs.neighbours_ref(X, plan.order, m)), (n, ndim, m)
+
+
+def test_forty_one_columns_are_refused_and_harm_nothing():
+    """MVC_MAXCOLS = 40 is a case; 41 is refused by ``VecchiaPlan.gram`` with a ValueError, by the library with MVC_EINVAL, and the valid
+    call that follows on the same plan returns the bits it returned before."""
+    case = lc.CASES["n129_exp3d_m40"]
+    X, W = lc.inputs(case)
+    W41 = np.hstack([W, W[:, :1]])
+    with vc.VecchiaPlan(X, m=30) as plan:
+        first = plan.gram(X, case["model"], case["par"], W)
+        with pytest.raises(ValueError, match="MVC_MAXCOLS"):
+            plan.gram(X, case["model"], case["par"], W41)
+        lib = vc.load()
+        ct, wt = np.ascontiguousarray(X.T), np.ascontiguousarray(W41.T)
+        out, ld, info = np.full((41, 41), 7.0), ctypes.c_double(7.0), ctypes.c_int32(-5)
+        rc = lib.mvc_plan_gram(plan._handle, ct.ctypes.data_as(vc._dp), lk.MODEL_IDS[case["model"]], *case["par"], wt.ctypes.data_as(vc._dp), 41,
+                               ctypes.byref(ld), out.ctypes.data_as(vc._dp), ctypes.byref(info))
+        assert rc == vc.MVC_EINVAL and b"MVC_MAXCOLS" in lib.mvc_last_error() and ld.value == 7.0 and np.all(out == 7.0)
+        again = plan.gram(X, case["model"], case["par"], W)
+    assert again[0] == first[0] and np.array_equal(again[1].view(np.int64), first[1].view(np.int64))
 
 
 def test_ties_go_to_the_smaller_position_and_every_order_is_served():
@@ -77,13 +111,17 @@ def test_gram_is_within_the_bar_symmetric_and_reproducible(name, m):
         logdet, G = plan.gram(X, case["model"], case["par"], W)
         again_logdet, again_G = plan.gram(X, case["model"], case["par"], W)
     el, eg = vcs.errors(logdet, G, ref_logdet, ref_G)
-    record("%-16s N %4d m %2d cols %2d kappa_2 %9.3g bar %9.3g logdet error %9.3g G error %9.3g worst/bar %8.3g"
-           % (name, case["n"], m, case["m"], kappa, bar, el, eg, max(el, eg) / bar))
+    edge = (name, m) in vcs.EDGE_DEVICE
+    record("%s%-16s N %4d m %2d cols %2d kappa_2 %9.3g bar %9.3g logdet error %9.3g G error %9.3g worst/bar %8.3g"
+           % ("vecchia   " if edge else "", name, case["n"], m, case["m"], kappa, bar, el, eg, max(el, eg) / bar), edge)
     assert G.shape == (case["m"], case["m"]) and np.array_equal(G, G.T)
     assert el <= bar and eg <= bar, (name, m, el, eg, bar)
     assert again_logdet == logdet and np.array_equal(again_G.view(np.int64), G.view(np.int64))  # the same bits
     if m >= case["n"] - 1:  # the exact likelihood: also held to the dense reference
-        dense_logdet, dense_G, _, dense_bar = lc.reference(name)
+        if name in lc.CASES:
+            dense_logdet, dense_G, _, dense_bar = lc.reference(name)
+        else:  # (a case of this module alone: the same brute force, the bar of the same kappa_2)
+            (dense_logdet, dense_G), dense_bar = lc.brute_force(X, case["model"], case["par"], W), bar
         el, eg = lc.errors(logdet, G, dense_logdet, dense_G)
         record("%-16s against the dense long-double reference: logdet error %9.3g G error %9.3g bar %9.3g" % (name, el, eg, dense_bar))
         assert el <= dense_bar and eg <= dense_bar
