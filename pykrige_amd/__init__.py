@@ -14,5 +14,15 @@ from ._lib import set_devices  # noqa: F401  (single-process multi-GPU: handles 
 from . import kriging_tools as kt  # noqa: F401  (the reference's alias)
 from . import ok, ok3d, uk, uk3d  # noqa: F401,E402  (`import pykrige; pykrige.ok.OrdinaryKriging` works upstream: pykrige/__init__.py:44-48 binds the submodules)
 
-__all__ = ["OrdinaryKriging", "UniversalKriging", "OrdinaryKriging3D", "UniversalKriging3D", "kt", "ok", "uk", "ok3d", "uk3d", "kriging_tools", "variography", "variography3d", "likelihood", "vecchia", "__version__"]
+__all__ = ["OrdinaryKriging", "UniversalKriging", "OrdinaryKriging3D", "UniversalKriging3D", "kt", "ok", "uk", "ok3d", "uk3d", "kriging_tools", "variography", "variography3d", "likelihood", "vecchia", "vecchia_grad", "__version__"]
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # vecchia_grad (Vecchia's objective with its analytic gradient and an L-BFGS-B fit: libmikvgrad.so) is imported on first use, not
+    # with the package: a process that never asks for it runs none of it
+    if name == "vecchia_grad":
+        import importlib
+
+        return importlib.import_module(".vecchia_grad", __name__)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1,6 +1,6 @@
 """What the ctypes bindings of the package's shared objects have in common: opening a library, the error mapping, the device number.
 
-Every binding module (_lib, variography, variography3d, likelihood, vecchia) keeps its own LIB_PATH, ABI_VERSION, SIGNATURES and cached
+Every binding module (_lib, variography, variography3d, likelihood, vecchia, vecchia_grad) keeps its own LIB_PATH, ABI_VERSION, SIGNATURES and cached
 ``_lib`` and hands them over at call time; nothing of a library is known here."""
 import ctypes as C
 import os

@@ -990,6 +990,40 @@ class _KrigingBase:
                                              start=self._list_parameters() if start is None else start, fit_anisotropy=fit_anisotropy,
                                              drift=drift, reml=reml, bounds=bounds, **anis)
 
+    # ---------------------------------------------------------------- ... with its analytic gradient (libmikvgrad.so, vecchia_grad.py)
+    def neg_log_likelihood_vecchia_grad(self, variogram_parameters=None, m=30, order="random", seed=0, plan=None, reml=True, **anisotropy):
+        """``nll, grad = obj.neg_log_likelihood_vecchia_grad(variogram_parameters=None, m=30, order="random", seed=0, plan=None,
+        reml=True, **anisotropy)``: what ``neg_log_likelihood_vecchia`` returns, bit for bit, and its analytic gradient from the same
+        local factorisations on the GPU (``pykrige_amd.vecchia_grad.neg_log_likelihood_vecchia_grad``).  grad is in natural units in the
+        order of ``pykrige_amd.likelihood.GRAD_NAMES_2D`` / ``GRAD_NAMES_3D``: psill (the partial sill, the nugget held), range, nugget,
+        then this class's anisotropy keywords, angles per degree.  plan: a ``VecchiaGradPlan`` of this object's adjusted stations to
+        reuse, else one is built and dropped.  The parameters, the anisotropy overrides, the trend (``regional_linear`` on the universal
+        classes) and the refusals are ``neg_log_likelihood``'s: 'linear', 'power' (ValueError) and 'custom' (NotImplementedError)
+        models, coordinates_type='geographic' and a handle that spans a device group (ValueError), any other drift term
+        (``NotImplementedError``) -- all before anything is loaded."""
+        from . import vecchia_grad
+
+        cols, v, drift, anis = self._likelihood_problem("neg_log_likelihood_vecchia_grad", anisotropy)
+        par = self._list_parameters() if variogram_parameters is None else variogram_parameters
+        return vecchia_grad.neg_log_likelihood_vecchia_grad(*cols, v, self.variogram_model, par, m=m, order=order, seed=seed, plan=plan,
+                                                            drift=drift, reml=reml, **anis)
+
+    def fit_variogram_vecchia_grad(self, m=30, order="random", seed=0, start=None, fit_anisotropy=False, reml=True, bounds=None,
+                                   **anisotropy):
+        """``fit_variogram_vecchia`` by a quasi-Newton search: ``fit = obj.fit_variogram_vecchia_grad(m=30, order="random", seed=0,
+        start=None, fit_anisotropy=False, reml=True, bounds=None, **anisotropy)``.  One ``VecchiaGradPlan`` built in the start metric
+        serves the whole L-BFGS-B search on the analytic gradient (``pykrige_amd.vecchia_grad.fit_variogram_vecchia_grad``), with the
+        Nelder-Mead finish of ``fit_variogram_ml(method='l-bfgs-b')``.  start=None begins at the object's current parameters and
+        anisotropy.  Returns ``pykrige_amd.likelihood.MLFit``; the object itself is not changed.  The trend (``regional_linear``) and
+        the refusals are those of ``neg_log_likelihood``: 'linear', 'power' and 'custom' models, coordinates_type='geographic', a
+        device group, and any other drift term (``NotImplementedError``)."""
+        from . import vecchia_grad
+
+        cols, v, drift, anis = self._likelihood_problem("fit_variogram_vecchia_grad", anisotropy)
+        return vecchia_grad.fit_variogram_vecchia_grad(*cols, v, self.variogram_model, m=m, order=order, seed=seed,
+                                                       start=self._list_parameters() if start is None else start,
+                                                       fit_anisotropy=fit_anisotropy, drift=drift, reml=reml, bounds=bounds, **anis)
+
     def _resident_problem(self, P, name, one_device):
         """The handle with this object's problem set (only if its key changed) and the points P loaded: (handle, factor key).
         _upload_and_factor without its factor(): mik_predict_cov / mik_predict_block refuse (an oversized P among the reasons) before

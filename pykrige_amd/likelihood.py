@@ -237,6 +237,33 @@ def nll_from_gram(n, logdet, G, nfields, reml, logdet_xtx):
     return out
 
 
+def nll_grad_from_gram(n, logdet, G, dlogdet, dG, nfields, reml, logdet_xtx):
+    """``nll, grad = nll_grad_from_gram(n, logdet, G, dlogdet, dG, nfields, reml, logdet_xtx)``: the negative log-likelihoods of
+    ``nll_from_gram`` -- its bits: it is called -- and their derivatives from ``dlogdet`` (K,) and ``dG`` (K, m, m), the derivatives of
+    ``logdet`` and ``G`` with respect to K parameters of the covariance, X held fixed.  The chain rule through the ML / REML algebra in
+    float64: with beta_f = G_xx^-1 G_xv[:, f],
+    dQ_f = dG_vv[f, f] - 2 dG_xv[:, f]^T beta_f + beta_f^T dG_xx beta_f,
+    ML: 1/2 [dlogdet + dQ_f];  REML: 1/2 [dlogdet + tr(G_xx^-1 dG_xx) + dQ_f].
+    grad is (F, K); each field is worked on its own.  Where ``nll_from_gram`` gives inf -- C or G_xx not positive definite -- nll is inf
+    and grad NaN."""
+    F = int(nfields)
+    nll = nll_from_gram(n, logdet, G, F, reml, logdet_xtx)
+    dlogdet, dG = np.asarray(dlogdet, dtype=np.float64), np.asarray(dG, dtype=np.float64)
+    K = dlogdet.shape[0]
+    grad = np.full((F, K), np.nan)
+    if not np.all(np.isfinite(nll)) or not (np.all(np.isfinite(dlogdet)) and np.all(np.isfinite(dG))):
+        return np.full(F, np.inf), grad
+    Li = np.linalg.inv(np.linalg.cholesky(G[F:, F:]))
+    Gi = Li.T @ Li
+    trace = [float(np.sum(Gi * dG[k][F:, F:])) if reml else 0.0 for k in range(K)]
+    for f in range(F):
+        beta = Gi @ np.ascontiguousarray(G[F:, f])
+        for k in range(K):
+            dq = float(dG[k][f, f]) - 2.0 * float(np.dot(np.ascontiguousarray(dG[k][F:, f]), beta)) + float(beta @ (dG[k][F:, F:] @ beta))
+            grad[f, k] = 0.5 * (float(dlogdet[k]) + trace[k] + dq)
+    return nll, grad
+
+
 def _internal_parameters(who, model, variogram_parameters):
     if variogram_parameters is None:
         raise ValueError("%s: variogram_parameters must be given (a list [sill, range, nugget] or a dict)" % who)
